@@ -20,6 +20,11 @@ value = peaks of all ranks / step time (max over ranks).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--spectra S]
        (N>1 under torch.distributed.run, one rank per GPU)
+       A plain run sets up, warms up, times the K steps (each settled against
+       its batch's reference pass) and prints the result line.
+       --full adds the per-kernel events and the roofline, the checks of the
+       results after the timed region, the engine counters and the CPU legs.
+       --dump-outputs DIR writes the last timed step's results (dump_outputs).
 """
 import argparse
 import json
@@ -57,6 +62,59 @@ def result_digest(r):
     from spectrseqtools_amd.parallel import canonical_digest
 
     return canonical_digest(r.status, r.count, r.offset, r.payload)
+
+
+DUMP_QUERIES = 2_000_000  # --dump-outputs: queries sampled per array
+DUMP_CAND_BYTES = 4_000_000  # and candidate bytes kept (48 MB in all at most)
+
+
+def dump_outputs(path, r, valid=None, suffix=""):
+    """--dump-outputs: the arrays a caller of the timed path holds after its
+    last step, as <name>.npy.  `r` is that step's fetched result, `valid` its
+    is_valid codes (config 3).  Arrays over DUMP_QUERIES entries are cut to a
+    fixed sample (seeded, ascending query order), the same for every run with
+    the same arguments:
+      a7_valid       float32  is_valid code per (breakage, peak) query
+      a8_status      float32  status per explain query
+      a8_count       float64  candidate count per explain query
+      a8_candidates  float32  the sampled SOME queries' candidate records
+                              (length byte + row indices) in query order, the
+                              first DUMP_CAND_BYTES of them
+    Payload offsets are layout, not answers (canonical_digest), and are left out."""
+    os.makedirs(path, exist_ok=True)
+
+    def sample(n):
+        if n <= DUMP_QUERIES:
+            return np.arange(n)
+        return np.sort(np.random.default_rng(20240229).choice(n, DUMP_QUERIES, replace=False))
+
+    def save(name, a):
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), a)
+
+    if valid is not None:
+        valid = np.asarray(valid)
+        save("a7_valid", valid[sample(len(valid))].astype(np.float32))
+    q = sample(len(r.status))
+    status = np.asarray(r.status, dtype=np.int8)[q]
+    save("a8_status", status.astype(np.float32))
+    save("a8_count", np.asarray(r.count)[q].astype(np.float64))
+    # each SOME query's records, walked as canonical_digest walks them
+    payload = np.asarray(r.payload, dtype=np.uint8)
+    qs = q[status == 2]
+    beg = np.asarray(r.offset)[qs].astype(np.int64)
+    c = np.asarray(r.count)[qs].astype(np.int64)
+    pos = beg.copy()
+    act = np.flatnonzero(c > 0)
+    k = 0
+    while len(act):
+        pos[act] += 1 + payload[pos[act]].astype(np.int64)
+        k += 1
+        act = act[c[act] > k]
+    ln = pos - beg
+    keep = np.cumsum(ln) <= DUMP_CAND_BYTES
+    beg, ln = beg[keep], ln[keep]
+    idx = np.repeat(beg - (np.cumsum(ln) - ln), ln) + np.arange(int(ln.sum()))
+    save("a8_candidates", payload[idx].astype(np.float32))
 
 
 def build_workload(n_spectra, seed, dp):
@@ -190,7 +248,14 @@ def main():
     ap.add_argument("--batches", type=int, default=3,
                     help="distinct config-3 batches cycled over the steps (>= 3: more inputs than the Infinity "
                          "Cache holds, so every step streams its inputs from HBM)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the per-kernel HIP events and the roofline, the "
+                         "checks of the timed steps' results against the reference pass (config 1: the oracle), "
+                         "the engine's counters and the CPU baseline legs.  Without it a run sets up, warms up, "
+                         "times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's results as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU baseline legs")
     ap.add_argument("--backend", default="nccl", choices=("nccl", "gloo"),
                     help="torch.distributed backend for N>1 (nccl = RCCL over xGMI; gloo: rehearsal of the "
                          "multi-rank path, e.g. several ranks on one GPU with SST_DEVICE=0)")
@@ -228,6 +293,10 @@ def main():
     args = ap.parse_args()
     if args.a7_stream:
         args.fused_step = 0  # A7 on its own stream: two launches
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        args.no_events = True  # the events feed the roofline, which --full reports
 
     import torch
 
@@ -409,13 +478,14 @@ def main():
     refs = []
     for b in range(R):
         rr = launch(b, outs7[0], None)
-        rr.fetch_device()
-        engine.synchronize()
-        a7_ok = np.array_equal(outs7[0][:n7s[b]].cpu().numpy(), wls[b]["a7_valid"])
-        if not a7_ok:
-            raise RuntimeError(f"batch {b}: is_valid bytes differ from the setup pass")
+        if args.full:
+            rr.fetch_device()
+            engine.synchronize()
+            a7_ok = np.array_equal(outs7[0][:n7s[b]].cpu().numpy(), wls[b]["a7_valid"])
+            if not a7_ok:
+                raise RuntimeError(f"batch {b}: is_valid bytes differ from the setup pass")
         expect[b] = rr.settle()
-        if rows_mode:
+        if rows_mode and args.full:
             # the device producers must issue exactly the host producers' queries:
             # the same answers as the explain pass over the host-built (mass,
             # threshold) pairs (which tests/test_gpu_fullsize.py checks against the oracle)
@@ -435,7 +505,7 @@ def main():
                      "canon": canonical_digest(rr.status, rr.count, rr.offset, rr.payload) if gath is not None
                      else None, "n_hits": expect[b][0],
                      "pair_hits": rr.pair_hits_device()[1] if args.fused_step else 0,
-                     "cap": None})
+                     "cap": None} if args.full else {"cap": None})
         if gath is not None:
             # the wire buffer's capacity: the fixed part (host-known from the
             # result's sizes) + a list slot for every query and hit (the bound
@@ -456,7 +526,8 @@ def main():
         torch.cuda.synchronize()
     for k in range(args.warmup):
         step(k)
-    drain(args.warmup - 1)
+    if args.warmup:
+        drain(args.warmup - 1)
     torch.cuda.synchronize()
     engine.synchronize()
 
@@ -504,15 +575,21 @@ def main():
     if gath is not None and settled["sent"] != args.steps:
         raise RuntimeError(f"{settled['sent']} of {args.steps} steps delivered to rank 0")
     for r, b in zip(results, batch_of):
-        if r is not None:
+        if r is not None and b is not None and args.full:
             r.fetch_device()
             if result_digest(r) != refs[b]["digest"] and not args.no_validate:
                 raise RuntimeError(f"a timed step's result (batch {b}) differs from the reference pass")
     engine.synchronize()
     for o, b in zip(outs7, batch_of):
-        assert np.array_equal(o[:n7s[b]].cpu().numpy(), wls[b]["a7_valid"]), \
+        assert not args.full or b is None or np.array_equal(o[:n7s[b]].cpu().numpy(), wls[b]["a7_valid"]), \
             "is_valid results changed between setup and timed runs"
-    if gath is not None:
+    if args.dump_outputs:
+        cur = (args.steps - 1) & 1
+        results[cur].fetch_device()
+        engine.synchronize()
+        dump_outputs(args.dump_outputs, results[cur], outs7[cur][:n7s[batch_of[cur]]].cpu().numpy(),
+                     suffix=f"_rank{rank}" if rank else "")
+    if gath is not None and args.full:
         # rank 0 decodes what it received from every rank in the last step:
         # each rank's result digest must match (and its A7 bytes)
         last_b = (args.steps - 1) % R
@@ -535,12 +612,62 @@ def main():
         if rank == 0 and gath is not None:
             np.savez(os.path.join(args.dump_gathered, "gathered.npz"), precs=precs,
                      **{f"rank{r_}": b_.cpu().numpy() for r_, b_ in enumerate(gath.last)})
-    for rf in refs:
+    for rf in refs if args.full else ():
         st = rf["status"]
         if (st < -2).any() and not args.no_validate:
             raise RuntimeError(f"internal statuses in results: {np.unique(st[st < -2])}")
 
     if rank != 0:
+        if dist:
+            dist.destroy_process_group()
+        return
+
+    ws_arr = np.asarray(wire_sizes, dtype=np.int64) if wire_sizes else None  # [delivered steps, ranks]
+    ms_step = 1e3 * elapsed / args.steps
+    value = peaks_all / (elapsed / args.steps)
+    head = {
+        "metric": METRIC,
+        "value": value,
+        "unit": "peaks/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_step,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u64",
+        "data": "synthetic",
+        "config": {
+            "workload": "config3: synthetic spectra (SURVEY 8(d)), full 104-mass/105-row alphabet, <=20-mer, "
+                        "A7 (4 breakages/peak) + A8 (sliding-window differences) per step",
+            "a8_source": ("rows: A7, classification filters, per-side SU order and sliding-window pairs formed on "
+                          "the device from the peaks inside each step (sst_step_rows_device)" if rows_mode else
+                          "queries: A8 (mass, threshold) pairs produced on the host before timing"),
+            "spectra_per_gpu": args.spectra,
+            "batches": (f"{R} distinct batches of {args.spectra} spectra (seeds {args.seed} + 7919 b), cycled "
+                        f"step by step, {sum(w['obs'].nbytes + w['a8_mass'].nbytes + w['a8_thr'].nbytes for w in wls) / 1e6:.0f} MB "
+                        f"of inputs: no step's inputs are still in the 256 MB Infinity Cache" if R > 1 else "1 batch"),
+            "peaks": peaks_all,
+            "a7_queries": n7_all,
+            "a8_queries": n8_all,
+            "max_len": seq.max_len,
+            "max_modifications": A,
+            "a7_stream": ("side stream, concurrent with the A8 chain" if args.a7_stream else "engine stream"),
+            "parallelism": ((f"spectra sharded over {world} GPUs; every step's complete result of every rank "
+                             f"gathered to rank 0 ({'RCCL' if args.backend == 'nccl' else 'gloo'}, wire format "
+                             f"v5, sst_wire_pack), overlapped with the next step"
+                             if gath is not None else f"spectra sharded over {world} GPUs, results kept per rank")
+                            if world > 1 else "1 GPU"),
+            "wire_bytes_per_rank_step": ({"mean": ws_arr.mean(axis=0).tolist(), "max": ws_arr.max(axis=0).tolist(),
+                                          "steps": int(len(ws_arr)),
+                                          "agreed": "per timed step: all_gather of each rank's packed size"}
+                                         if ws_arr is not None else None),
+        },
+    }
+    queries_per_s = (n7_all + n8_all) / (elapsed / args.steps)
+    if not args.full:  # the plain run ends here: the headline figure alone
+        print(json.dumps({**head, "queries_per_s": queries_per_s}), flush=True)
         if dist:
             dist.destroy_process_group()
         return
@@ -649,9 +776,6 @@ def main():
     res = results[(args.steps - 1) & 1]
     some = (st == 2) | (st == -2)
     n_hits0 = refs[timed_batches[-1]]["n_hits"]
-    ws_arr = np.asarray(wire_sizes, dtype=np.int64) if wire_sizes else None  # [delivered steps, ranks]
-    ms_step = 1e3 * elapsed / args.steps
-    value = peaks_all / (elapsed / args.steps)
 
     cpu = None
     lit_frac = None
@@ -662,44 +786,7 @@ def main():
             lit_frac = lit_bytes / (dus * 1e-6) / 1e9 / HBM_PEAK_GBPS
 
     line = {
-        "metric": METRIC,
-        "value": value,
-        "unit": "peaks/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_step,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u64",
-        "data": "synthetic",
-        "config": {
-            "workload": "config3: synthetic spectra (SURVEY 8(d)), full 104-mass/105-row alphabet, <=20-mer, "
-                        "A7 (4 breakages/peak) + A8 (sliding-window differences) per step",
-            "a8_source": ("rows: A7, classification filters, per-side SU order and sliding-window pairs formed on "
-                          "the device from the peaks inside each step (sst_step_rows_device)" if rows_mode else
-                          "queries: A8 (mass, threshold) pairs produced on the host before timing"),
-            "spectra_per_gpu": args.spectra,
-            "batches": (f"{R} distinct batches of {args.spectra} spectra (seeds {args.seed} + 7919 b), cycled "
-                        f"step by step, {sum(w['obs'].nbytes + w['a8_mass'].nbytes + w['a8_thr'].nbytes for w in wls) / 1e6:.0f} MB "
-                        f"of inputs: no step's inputs are still in the 256 MB Infinity Cache" if R > 1 else "1 batch"),
-            "peaks": peaks_all,
-            "a7_queries": n7_all,
-            "a8_queries": n8_all,
-            "max_len": seq.max_len,
-            "max_modifications": A,
-            "a7_stream": ("side stream, concurrent with the A8 chain" if args.a7_stream else "engine stream"),
-            "parallelism": ((f"spectra sharded over {world} GPUs; every step's complete result of every rank "
-                             f"gathered to rank 0 ({'RCCL' if args.backend == 'nccl' else 'gloo'}, wire format "
-                             f"v5, sst_wire_pack), overlapped with the next step"
-                             if gath is not None else f"spectra sharded over {world} GPUs, results kept per rank")
-                            if world > 1 else "1 GPU"),
-            "wire_bytes_per_rank_step": ({"mean": ws_arr.mean(axis=0).tolist(), "max": ws_arr.max(axis=0).tolist(),
-                                          "steps": int(len(ws_arr)),
-                                          "agreed": "per timed step: all_gather of each rank's packed size"}
-                                         if ws_arr is not None else None),
-        },
+        **head,
         "roofline": {
             "bound": "hbm",
             "kernel": ("k_rows_count_w + k_rows_emit_w (+ k_rows_count / k_rows_emit for spectra over 160 peaks: "
@@ -736,7 +823,7 @@ def main():
                  "k_is_valid + k_explain_scan + k_result_pack") +
                 " per step: status bytes, dense hit list and dense payload of every query (the complete "
                 "result); the host settles step k-1 while step k runs",
-        "queries_per_s": (n7_all + n8_all) / (elapsed / args.steps),
+        "queries_per_s": queries_per_s,
         "cpu_baseline": cpu,
     }
     print(json.dumps(line), flush=True)
@@ -797,8 +884,9 @@ def main_config1(args, engine, dist, rank, world, dev_t):
         return res
 
     res = step(None)
-    res.fetch_device()
-    ref_st, ref_cnt = res.status.copy(), res.count.copy()
+    if args.full:
+        res.fetch_device()
+        ref_st, ref_cnt = res.status.copy(), res.count.copy()
     for k in range(args.warmup):
         res = step(res)
     engine.synchronize()
@@ -817,23 +905,27 @@ def main_config1(args, engine, dist, rank, world, dev_t):
     elapsed = time.perf_counter() - t0
     prof = engine.profile_read() if not args.no_events else {}
     engine.profile(False)
-    res.fetch_device()
-    if not (np.array_equal(res.status, ref_st) and np.array_equal(res.count, ref_cnt)):
-        raise RuntimeError("a timed config-1 step's result differs from the reference pass")
-    # parity sample against the CPU oracle (the checker, outside the timed region)
-    sys.path.insert(0, os.path.join(REPO, "tests"))
-    import _oracle as oracle
+    if args.full or args.dump_outputs:
+        res.fetch_device()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, suffix=f"_rank{rank}" if rank else "")
+    if args.full:
+        if not (np.array_equal(res.status, ref_st) and np.array_equal(res.count, ref_cnt)):
+            raise RuntimeError("a timed config-1 step's result differs from the reference pass")
+        # parity sample against the CPU oracle (the checker, outside the timed region)
+        sys.path.insert(0, os.path.join(REPO, "tests"))
+        import _oracle as oracle
 
-    ms = [m.mass for m in dp.masses]
-    table = oracle.build_table(ms, max(ms) * 35, 32)
-    alph = oracle.Alphabet(ms, [m.is_modification for m in dp.masses],
-                           [round(seq.max_len * m.modification_rate) for m in dp.masses])
-    sample = np.unique(np.concatenate([np.arange(min(n, 21)), np.random.default_rng(3).integers(0, n, 400)]))
-    for i in sample:
-        st, sols, n_empty, _ = oracle.explain_table(table, 32, alph, mass[i], thr[i], dp.tolerance, int(mods[i]))
-        if sorted(res.candidates(i)) != sorted(sols) and not args.no_validate:
-            raise RuntimeError(f"config-1 query {i} differs from the oracle")
-    stats = res.stats()
+        ms = [m.mass for m in dp.masses]
+        table = oracle.build_table(ms, max(ms) * 35, 32)
+        alph = oracle.Alphabet(ms, [m.is_modification for m in dp.masses],
+                               [round(seq.max_len * m.modification_rate) for m in dp.masses])
+        sample = np.unique(np.concatenate([np.arange(min(n, 21)), np.random.default_rng(3).integers(0, n, 400)]))
+        for i in sample:
+            st, sols, n_empty, _ = oracle.explain_table(table, 32, alph, mass[i], thr[i], dp.tolerance, int(mods[i]))
+            if sorted(res.candidates(i)) != sorted(sols) and not args.no_validate:
+                raise RuntimeError(f"config-1 query {i} differs from the oracle")
+        stats = res.stats()
     if dist:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev_t)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -842,7 +934,19 @@ def main_config1(args, engine, dist, rank, world, dev_t):
         if dist:
             dist.destroy_process_group()
         return
-    n_def = int(stats[1] + stats[2] + stats[3])
+    head = {
+        "metric": METRIC, "value": n * world / (elapsed / args.steps), "unit": "peaks/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
+        "config": {"workload": "config1: whole masses of random canonical 1..8-mers (+ the reference test's 7 x 3), "
+                               "canonical 5-row table, budget round(0.5 len) per query", "queries_per_gpu": n},
+    }
+    if not args.full:  # the plain run ends here
+        print(json.dumps(head), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
+    n_def =int(stats[1] + stats[2] + stats[3])
     nodes = int(stats[4])
     some = res.status == _native.SST_SOME
     # algorithmic bytes of the deferred launch: each routed query's window
@@ -884,11 +988,7 @@ def main_config1(args, engine, dist, rank, world, dev_t):
         cpu["single_core"] = out[1]
         cpu["reference_python_single_core"] = {"value": 904.0, "unit": "peaks/s", "source": "BASELINE.md config 1"}
     print(json.dumps({
-        "metric": METRIC, "value": n * world / (elapsed / args.steps), "unit": "peaks/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
-        "config": {"workload": "config1: whole masses of random canonical 1..8-mers (+ the reference test's 7 x 3), "
-                               "canonical 5-row table, budget round(0.5 len) per query", "queries_per_gpu": n},
+        **head,
         "roofline": {"bound": "hbm", "kernel": "k_explain_deferred", "achieved": achieved, "peak": HBM_PEAK_GBPS,
                      "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
                      "traffic_source": traffic_src, "algorithmic_bytes_per_launch": bytes_def, "avg_launch_us": dus,

@@ -35,7 +35,10 @@ def golden_tables():
 
 @pytest.fixture(scope="session")
 def golden_cases():
-    return load_golden("explain_cases.json.gz")
+    # stored in parts of consecutive cases (make_golden.py dump_cases); the contexts are in part 0
+    names = sorted(n for n in os.listdir(GOLDEN) if n.startswith("explain_cases.part"))
+    parts = [load_golden(n) for n in names]
+    return {"contexts": parts[0]["contexts"], "cases": [c for p in parts for c in p["cases"]]}
 
 
 @pytest.fixture(scope="session")

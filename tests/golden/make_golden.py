@@ -14,7 +14,8 @@ own code.
 Outputs (all JSON, floats written with repr so they round-trip exactly):
   alphabet.json        EXPLANATION_MASSES rows, breakage dicts, constants
   tables.json          SHA-256 of reference-built packed tables + tiny tables verbatim
-  explain_cases.json.gz explain_mass_with_table / _with_recursion / is_valid_mass /
+  explain_cases.part[0-3].json.gz
+                       explain_mass_with_table / _with_recursion / is_valid_mass /
                        compute_sequence_length_bound known answers
   population.json.gz   A7 (is_valid) and A8 (adjacent-difference explain) query
                        streams of the reference's own test spectra
@@ -68,6 +69,22 @@ def dump(name, obj, gz=False):
         with open(path, "wb") as f:
             f.write(data)
     print(f"wrote {name} ({len(data) / 1e6:.2f} MB raw)", flush=True)
+
+
+CASE_PARTS = 4  # explain_cases.partK.json.gz: each well under 1 MiB
+
+
+def dump_cases(contexts, cases):
+    """The known-answer cases in CASE_PARTS files of consecutive cases and
+    about equal raw size (conftest.py's golden_cases joins them in order);
+    the contexts travel in part 0."""
+    sizes = np.cumsum([len(json.dumps(c, separators=(",", ":"))) for c in cases])
+    cuts = [0] + [int(np.searchsorted(sizes, sizes[-1] * k / CASE_PARTS)) for k in range(1, CASE_PARTS)] + [len(cases)]
+    for k in range(CASE_PARTS):
+        part = {"cases": cases[cuts[k]:cuts[k + 1]]}
+        if k == 0:
+            part = {"contexts": contexts, **part}
+        dump(f"explain_cases.part{k}.json.gz", part, gz=True)
 
 
 # --------------------------------------------------------------------------
@@ -339,7 +356,7 @@ def cases():
         out.append(dict(run_valid(dp, cid, m, None), tag="config1/is_valid"))
     del dp
     print(f"  config1 n={len(out)}", flush=True)
-    dump("explain_cases.json.gz", {"contexts": CTX, "cases": out}, gz=True)
+    dump_cases(CTX, out)
 
 
 # --------------------------------------------------------------------------

@@ -205,7 +205,7 @@ def test_raise_cases_type_and_message(golden_raise_cases):
 
 
 def test_golden_raise_cases_through_mirror(golden_cases):
-    """Every explain_cases.json.gz case with status "raise" through the
+    """Every explain_cases.part*.json.gz case with status "raise" through the
     mirror's explain_mass_with_table / is_valid_mass: the reference's
     exception type (NotImplementedError), never NameError."""
     from spectrseqtools_amd.mass_explanation import explain_mass_with_table, is_valid_mass

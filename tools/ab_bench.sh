@@ -5,6 +5,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 R=$1; shift
+AB_ARGS="--full $AB_ARGS"  # the launch times printed below come from the roofline
 for r in $(seq 1 $R); do
   for lib in "$@"; do
     tag=$(basename $lib .so)

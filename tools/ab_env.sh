@@ -4,6 +4,7 @@
 # interleaved over 3 rounds.  usage: ab_env.sh TAG base SST_PACK_DBG=1 ...
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"; mkdir -p gpurun_out
 TAG=$1; shift
+BENCH_EXTRA="--full $BENCH_EXTRA"  # the launch times printed below come from the roofline
 for r in 1 2 3; do
   for v in "$@"; do
     if [ "$v" = base ]; then envs=""; else envs="$v"; fi
