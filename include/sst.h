@@ -817,6 +817,55 @@ typedef struct sst_post_args {
 } sst_post_args;
 int sst_post_skeleton_device(sst_table* t, const sst_post_args* a);
 
+/* The dense per-spectrum hand-off to the MILP stages: what Predictor.predict
+ * holds after the skeleton-based reduction (prediction.py:88-103 -- the
+ * fragments build_skeleton returned, skeleton_building.py:67-109, that pass
+ * the reduced alphabet's is_valid filter, with min_end / max_end; the
+ * combined skeleton's seq_len positions), compacted so that one download per
+ * array delivers it.  Count, then emit, as sst_bins_count_device /
+ * sst_bins_emit_device:
+ * sst_handoff_count_device: n_frag[g] = the row slots of spectrum g with a
+ * non-zero flags byte among its cnt[g] rows from slot 4 * peak_off[g],
+ * n_pos[g] = seq_len[g]; both 0 where active[g] == 0; then their exclusive
+ * prefixes frag_off / pos_off (n_spec + 1 entries each, totals last).
+ * sst_handoff_emit_device (after the caller sized the outputs from the
+ * totals): the flagged rows of spectrum g in ascending row order from
+ * frag_off[g] -- index (the row's place among the spectrum's rows: the
+ * reference's SU-order `index`, prediction.py:68-72), code (meta & 0x1f:
+ * breakage code, side bits << 2, singleton << 4), su, obs, out_min_end,
+ * out_max_end -- and the first seq_len[g] position masks (two u64 each) of
+ * comb + 2 comb_off[g] at skeleton + 2 pos_off[g].  flags / min_end / max_end
+ * are row-slot arrays (sst_post_args' alive_out / min_end_out / max_end_out).
+ * Device pointers, the ctx's stream. */
+typedef struct sst_handoff_args {
+  int64_t n_spec;
+  const int64_t* peak_off;   /* [n_spec + 1] */
+  const uint32_t* cnt;       /* [n_spec] rows per spectrum */
+  const double* r_su;        /* row slots, as sst_classify_rows_device writes them */
+  const double* r_ob;
+  const uint32_t* r_meta;
+  const uint8_t* flags;      /* row slots: the rows to hand off */
+  const int32_t* min_end;    /* row slots */
+  const int32_t* max_end;
+  const uint8_t* active;     /* [n_spec] */
+  const int32_t* seq_len;    /* [n_spec] */
+  const uint64_t* comb_off;  /* [n_spec] as sst_jaccard_args.comb_off */
+  const uint64_t* comb;
+  uint32_t* n_frag;          /* [n_spec] count pass */
+  uint32_t* n_pos;
+  uint64_t* frag_off;        /* [n_spec + 1] count pass writes, emit pass reads */
+  uint64_t* pos_off;
+  int32_t* index;            /* [frag_off[n_spec]] emit pass (may be NULL for the count pass) */
+  uint8_t* code;
+  double* su;
+  double* obs;
+  int32_t* out_min_end;
+  int32_t* out_max_end;
+  uint64_t* skeleton;        /* [2 pos_off[n_spec]] */
+} sst_handoff_args;
+int sst_handoff_count_device(sst_table* t, const sst_handoff_args* a);
+int sst_handoff_emit_device(sst_table* t, const sst_handoff_args* a);
+
 /* compute_sequence_length_bound (mass_table.py:343-487) after the skeleton's
  * alphabet reduction (skeleton_building.py:315-336), both directions, for
  * queries on per-spectrum reduced alphabets, exact without a table rebuild:
@@ -935,6 +984,7 @@ int64_t sst_pyset_order(const int32_t* keys, const int64_t* hashes, int64_t n, i
 #define SST_K_JACCARD 16      /* k_jaccard (sst_jaccard_device) */
 #define SST_K_PAIRS_ALPHA 17  /* k_pairs_alpha (sst_explain_pairs_alpha*) */
 #define SST_K_REQUERY_MERGE 18 /* k_requery_count + k_scan_u32 + k_requery_copy (sst_requery_merge_device) */
+#define SST_K_HANDOFF 19 /* k_handoff_count + k_scan_u32, k_handoff_emit (sst_handoff_*_device) */
 #define SST_K_COUNT 24
 /* When enabled, every kernel launch of this ctx is bracketed by hipEvents
  * recorded on the ctx stream; sst_profile_read synchronises and returns the

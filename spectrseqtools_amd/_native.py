@@ -38,13 +38,14 @@ EXPORTS = (
     "sst_reach_rows_device", "sst_length_bounds_reach_device", "sst_jaccard_device", "sst_skeleton_alpha_device",
     "sst_dict_list_device", "sst_fix_finish_device", "sst_pipe_reserve_rows", "sst_reach_lowest_device",
     "sst_length_bounds_frontier_device", "sst_post_skeleton_device", "sst_ctx_trim", "sst_requery_merge_device",
+    "sst_handoff_count_device", "sst_handoff_emit_device",
 )
 
 # kernel ids of sst_profile_read
 K_IS_VALID, K_EXPLAIN_SCAN, K_EXPLAIN_DEEP, K_EXPLAIN_NOMEMO, K_EXPLAIN_EXACT, K_EXPLAIN_EXPAND = 0, 1, 2, 3, 4, 5
 K_RESULT_PACK = 6
 (K_CLASSIFY_ROWS, K_FIX_ROUND, K_VALID_ALPHA, K_BINS_COUNT, K_BINS_EMIT, K_DICT, K_SKEL_WALK, K_REACH_ROWS,
- K_LENGTH_BOUND, K_JACCARD, K_PAIRS_ALPHA, K_REQUERY_MERGE) = range(7, 19)
+ K_LENGTH_BOUND, K_JACCARD, K_PAIRS_ALPHA, K_REQUERY_MERGE, K_HANDOFF) = range(7, 20)
 K_COUNT = 24  # SST_K_COUNT
 KERNEL_NAMES = {K_IS_VALID: "k_is_valid", K_EXPLAIN_SCAN: "k_explain_scan", K_EXPLAIN_DEEP: "k_explain_deferred",
                 K_EXPLAIN_EXPAND: "k_explain_expand",
@@ -52,7 +53,8 @@ KERNEL_NAMES = {K_IS_VALID: "k_is_valid", K_EXPLAIN_SCAN: "k_explain_scan", K_EX
                 K_CLASSIFY_ROWS: "k_classify_rows", K_FIX_ROUND: "k_fix_round", K_VALID_ALPHA: "k_valid_alpha",
                 K_BINS_COUNT: "k_bins_count", K_BINS_EMIT: "k_bins_emit", K_DICT: "k_dict_build",
                 K_SKEL_WALK: "k_skel_walk", K_REACH_ROWS: "k_reach_rows", K_LENGTH_BOUND: "k_length_bound",
-                K_JACCARD: "k_jaccard", K_PAIRS_ALPHA: "k_pairs_alpha", K_REQUERY_MERGE: "k_requery_merge"}
+                K_JACCARD: "k_jaccard", K_PAIRS_ALPHA: "k_pairs_alpha", K_REQUERY_MERGE: "k_requery_merge",
+                K_HANDOFF: "k_handoff"}
 
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
@@ -92,6 +94,15 @@ class PostArgs(ctypes.Structure):
                 ("comb", ctypes.c_void_p), ("alpha", ctypes.c_void_p), ("alpha_out", ctypes.c_void_p),
                 ("active", ctypes.c_void_p), ("alive_out", ctypes.c_void_p), ("min_end_out", ctypes.c_void_p),
                 ("max_end_out", ctypes.c_void_p), ("err", ctypes.c_void_p)]
+
+
+class HandoffArgs(ctypes.Structure):
+    """sst_handoff_args (include/sst.h): the dense per-spectrum hand-off to the MILP stages."""
+    _fields_ = [("n_spec", ctypes.c_int64)] + \
+        [(n, ctypes.c_void_p) for n in ("peak_off", "cnt", "r_su", "r_ob", "r_meta", "flags", "min_end", "max_end",
+                                        "active", "seq_len", "comb_off", "comb", "n_frag", "n_pos", "frag_off",
+                                        "pos_off", "index", "code", "su", "obs", "out_min_end", "out_max_end",
+                                        "skeleton")]
 
 
 class RequeryMergeArgs(ctypes.Structure):
@@ -303,6 +314,10 @@ def load_library(path=LIB_PATH):
     lib.sst_post_skeleton_device.restype = _I
     lib.sst_requery_merge_device.argtypes = [_P, ctypes.POINTER(RequeryMergeArgs), _P, _P]
     lib.sst_requery_merge_device.restype = _I
+    lib.sst_handoff_count_device.argtypes = [_P, ctypes.POINTER(HandoffArgs)]
+    lib.sst_handoff_count_device.restype = _I
+    lib.sst_handoff_emit_device.argtypes = [_P, ctypes.POINTER(HandoffArgs)]
+    lib.sst_handoff_emit_device.restype = _I
     lib.sst_jaccard_device.argtypes = [_P, ctypes.POINTER(JaccardArgs)]
     lib.sst_jaccard_device.restype = _I
     lib.sst_skeleton_alpha_device.argtypes = [_P, _I64, _P, _P, _P, _P, _P]

@@ -3613,6 +3613,35 @@ extern "C" int sst_post_skeleton_device(sst_table* t, const sst_post_args* a) {
   return SST_OK;
 }
 
+static bool handoff_inputs_ok(const sst_handoff_args* a) {
+  return a->peak_off && a->cnt && a->flags && a->active && a->seq_len && a->frag_off && a->pos_off;
+}
+
+extern "C" int sst_handoff_count_device(sst_table* t, const sst_handoff_args* a) {
+  if (!t || !a || a->n_spec < 0 || a->n_spec > INT32_MAX || !a->frag_off || !a->pos_off) return SST_E_ARG;
+  if (a->n_spec > 0 && (!handoff_inputs_ok(a) || !a->n_frag || !a->n_pos)) return SST_E_ARG;
+  sst_ctx* c = t->ctx;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  if (int rc = set_device(c)) return rc;
+  Prof p(c, SST_K_HANDOFF);
+  HIP_OK(c, sst::launch_handoff_count(*a, 8 * c->n_cu, c->stream));
+  return SST_OK;
+}
+
+extern "C" int sst_handoff_emit_device(sst_table* t, const sst_handoff_args* a) {
+  if (!t || !a || a->n_spec < 0 || a->n_spec > INT32_MAX) return SST_E_ARG;
+  if (a->n_spec == 0) return SST_OK;
+  if (!handoff_inputs_ok(a) || !a->r_su || !a->r_ob || !a->r_meta || !a->min_end || !a->max_end || !a->comb_off ||
+      !a->comb || !a->index || !a->code || !a->su || !a->obs || !a->out_min_end || !a->out_max_end || !a->skeleton)
+    return SST_E_ARG;
+  sst_ctx* c = t->ctx;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  if (int rc = set_device(c)) return rc;
+  Prof p(c, SST_K_HANDOFF);
+  HIP_OK(c, sst::launch_handoff_emit(*a, 8 * c->n_cu, c->stream));
+  return SST_OK;
+}
+
 extern "C" int sst_skeleton_alpha_device(sst_table* t, int64_t n_spec, const int32_t* d_max_len,
                                          const uint64_t* d_skel_off, const uint64_t* d_skel, const uint64_t* d_alpha,
                                          uint64_t* d_out) {

@@ -13,6 +13,12 @@ SU order of its classify_fragments frame, so a row's slot offset is the
 the device memory, plus the index gathers that set up a masked-explain pass's
 per-query budget rows (_lens_pass); every stage's computation -- the rounds'
 re-query merge included (sst_requery_merge_device) -- is the library's.
+
+run_batch is the one call over a batch: the six stages, then the dense
+per-spectrum hand-off to the MILP stages (sst_handoff_count_device /
+sst_handoff_emit_device, csrc/sst_handoff.hip) as a BatchOutcome of host
+arrays; a spectrum outside a per-spectrum engine limit (DeviceLimits) runs
+the host mirror instead and is spliced in at its position.
 """
 import ctypes
 import os
@@ -1387,3 +1393,458 @@ def unpack_outcomes(buf):
     if o != len(b):
         raise ValueError("outcome buffer size mismatch")
     return out
+
+
+# ---------------------------------------------------------------------------
+# The whole batch in one call, with the dense per-spectrum hand-off to the
+# MILP stages (prediction.py:112-168): sst_handoff_count_device /
+# sst_handoff_emit_device (csrc/sst_handoff.hip), BatchOutcome, run_batch
+# ---------------------------------------------------------------------------
+HANDOFF_MAGIC = 0x4F485453  # "STHO"
+ROUTE_DEVICE, ROUTE_MIRROR = 0, 1
+REASON_PEAKS, REASON_MAX_LEN, REASON_WALK, REASON_FRONTIER = 1, 2, 4, 8
+REASON_NAMES = {REASON_PEAKS: "more peaks than limits.max_peaks", REASON_MAX_LEN: "max_len above limits.max_len",
+                REASON_WALK: "a side's skeleton walk outgrew the walk capacities",
+                REASON_FRONTIER: "the length bounds' frontier outgrew its workspace"}
+
+
+@dataclass(frozen=True)
+class DeviceLimits:
+    """The device engines' per-spectrum limits; a spectrum outside
+    one is routed to the host mirror by run_batch.  The defaults are the
+    engines' own values."""
+    max_peaks: int = MAX_PEAKS         # peaks per spectrum (classify_device)
+    max_len: int = 253                 # skeleton walk / frontier value range
+    walk_caps: tuple = (64, 32)        # skeleton_device caps
+    walk_big_caps: tuple = (8192, 8192)  # skeleton_device big_caps
+    walk_max_rounds: int = 4096        # skeleton_device max_rounds
+    frontier_workspace: int = 0        # length_device frontier_workspace (0: the engine's default)
+
+
+@_one_stream
+def handoff_device(dp_table, rows: DeviceRows, ln: DeviceLength, post: DevicePost, active=None):
+    """The hand-off kernels over a batch the six stages have run: the
+    fragments that survive the skeleton-based reduction (post.alive) of every
+    active spectrum, compacted per spectrum in row order with min_end /
+    max_end, and the combined skeleton's seq_len positions
+    (sst_handoff_count_device, one 16-byte read of the totals,
+    sst_handoff_emit_device), then one download per output array.  active:
+    [S] spectra to hand off (default post.active).  Returns a dict of host
+    numpy arrays (frag_off, pos_off, index, code, su, obs, min_end, max_end,
+    skeleton [total, 2] u64) and "bytes", the bytes the downloads moved."""
+    import torch
+
+    dt = dp_table.device_table
+    eng = dt.engine
+    L = eng._lib
+    S = len(ln.seq_len)
+    dev = rows.su.device
+    act = np.ascontiguousarray(post.active if active is None else active, dtype=np.uint8)[:S]
+    act_t = torch.as_tensor(act if S else np.zeros(1, np.uint8), device=dev)
+    sl_t = torch.as_tensor(np.ascontiguousarray(ln.seq_len, dtype=np.int32) if S else np.zeros(1, np.int32),
+                           device=dev)
+    co_t = torch.as_tensor(np.ascontiguousarray(ln.comb_off, dtype=np.int64), device=dev)
+    n_frag = torch.zeros(max(1, S), dtype=torch.int32, device=dev)
+    n_pos = torch.zeros(max(1, S), dtype=torch.int32, device=dev)
+    off = torch.zeros((2, S + 1), dtype=torch.int64, device=dev)  # frag_off, pos_off
+    a = _native.HandoffArgs()
+    a.n_spec = S
+    a.peak_off, a.cnt = rows.peak_off.data_ptr(), rows.rows.data_ptr()
+    a.r_su, a.r_ob, a.r_meta = rows.su.data_ptr(), rows.obs.data_ptr(), rows.meta.data_ptr()
+    a.flags, a.min_end, a.max_end = post.alive.data_ptr(), post.min_end.data_ptr(), post.max_end.data_ptr()
+    a.active, a.seq_len, a.comb_off, a.comb = act_t.data_ptr(), sl_t.data_ptr(), co_t.data_ptr(), ln.comb.data_ptr()
+    a.n_frag, a.n_pos = n_frag.data_ptr(), n_pos.data_ptr()
+    a.frag_off, a.pos_off = off[0].data_ptr(), off[1].data_ptr()
+    torch.cuda.synchronize(dev)
+    eng.check(L.sst_handoff_count_device(dt.handle, ctypes.byref(a)), "sst_handoff_count_device")
+    eng.synchronize()
+    off_h = off.cpu().numpy()
+    nf, npos = int(off_h[0, S]), int(off_h[1, S])
+    index = torch.empty(max(1, nf), dtype=torch.int32, device=dev)
+    code = torch.empty(max(1, nf), dtype=torch.uint8, device=dev)
+    su = torch.empty(max(1, nf), dtype=torch.float64, device=dev)
+    ob = torch.empty(max(1, nf), dtype=torch.float64, device=dev)
+    lo = torch.empty(max(1, nf), dtype=torch.int32, device=dev)
+    hi = torch.empty(max(1, nf), dtype=torch.int32, device=dev)
+    skel = torch.empty((max(1, npos), 2), dtype=torch.int64, device=dev)
+    a.index, a.code, a.su, a.obs = index.data_ptr(), code.data_ptr(), su.data_ptr(), ob.data_ptr()
+    a.out_min_end, a.out_max_end, a.skeleton = lo.data_ptr(), hi.data_ptr(), skel.data_ptr()
+    eng.check(L.sst_handoff_emit_device(dt.handle, ctypes.byref(a)), "sst_handoff_emit_device")
+    eng.synchronize()
+    out = {"frag_off": off_h[0].copy(), "pos_off": off_h[1].copy(), "index": index[:nf].cpu().numpy(),
+           "code": code[:nf].cpu().numpy(), "su": su[:nf].cpu().numpy(), "obs": ob[:nf].cpu().numpy(),
+           "min_end": lo[:nf].cpu().numpy(), "max_end": hi[:nf].cpu().numpy(),
+           "skeleton": skel[:npos].cpu().numpy().view(np.uint64)}
+    out["bytes"] = int(sum(v.nbytes for v in out.values()))
+    return out
+
+
+def _row_names(dp_table):
+    from .mass_explanation import MASS_NAMES
+
+    return [""] + [MASS_NAMES[m.mass][0] for m in dp_table.masses[1:]]
+
+
+def _segments(off, idx):
+    """Source positions of segments idx of a ragged array with offsets off,
+    concatenated in that order, and the new offsets."""
+    off = np.asarray(off, dtype=np.int64)
+    n = (off[1:] - off[:-1])[idx]
+    new = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+    src = np.repeat(off[:-1][idx] - new[:-1], n) + np.arange(int(new[-1]), dtype=np.int64)
+    return src, new
+
+
+@dataclass
+class BatchOutcome:
+    """What Predictor.predict holds for every spectrum of a batch when it
+    reaches its MILP stages (prediction.py:112-168), as host numpy arrays
+    (no device reference is kept): per spectrum whether predict returns
+    Prediction.default() (build_skeleton raised; such a spectrum has no
+    positions, no fragments and a zero alphabet), where it was computed
+    (route / reason), the alphabet after the skeleton-based reduction, the
+    skeleton sequence (position masks over the table's rows) and the
+    surviving fragments with min_end / max_end, both dense."""
+    default: np.ndarray       # [S] bool
+    route: np.ndarray         # [S] u8 ROUTE_DEVICE / ROUTE_MIRROR
+    reason: np.ndarray        # [S] u8 REASON_* bits (0 on the device route)
+    alpha: np.ndarray         # [S, 2] u64 row masks of the table
+    seq_len: np.ndarray       # [S] i32
+    pos_off: np.ndarray       # [S + 1] i64
+    skeleton: np.ndarray      # [pos_off[S], 2] u64 row masks per position
+    frag_off: np.ndarray      # [S + 1] i64
+    frag_index: np.ndarray    # i32: the fragment's `index` (prediction.py:68-72)
+    frag_code: np.ndarray     # u8: breakage code | START << 2 | END << 3 | singleton << 4
+    frag_su: np.ndarray       # f64 standard_unit_mass
+    frag_obs: np.ndarray      # f64 observed_mass
+    frag_min_end: np.ndarray  # i32
+    frag_max_end: np.ndarray  # i32
+    breakage_names: list      # breakage label per code
+    row_names: list           # nucleoside name per table row ("" for row 0)
+    row_mass: np.ndarray      # [rows] i64 integer mass per table row
+
+    SPECTRUM_FIELDS = ("default", "route", "reason", "alpha", "seq_len")
+    POSITION_FIELDS = ("skeleton",)
+    FRAGMENT_FIELDS = ("frag_index", "frag_code", "frag_su", "frag_obs", "frag_min_end", "frag_max_end")
+    _DTYPES = {"default": np.bool_, "route": np.uint8, "reason": np.uint8, "alpha": np.uint64, "seq_len": np.int32,
+               "pos_off": np.int64, "skeleton": np.uint64, "frag_off": np.int64, "frag_index": np.int32,
+               "frag_code": np.uint8, "frag_su": np.float64, "frag_obs": np.float64, "frag_min_end": np.int32,
+               "frag_max_end": np.int32, "row_mass": np.int64}
+
+    def __post_init__(self):
+        for k, dt in self._DTYPES.items():
+            setattr(self, k, np.ascontiguousarray(getattr(self, k), dtype=dt))
+        self.alpha = self.alpha.reshape(-1, 2)
+        self.skeleton = self.skeleton.reshape(-1, 2)
+        self.breakage_names = list(self.breakage_names)
+        self.row_names = list(self.row_names)
+        S = len(self.default)
+        if not (len(self.route) == len(self.reason) == len(self.alpha) == len(self.seq_len) == S and
+                len(self.pos_off) == len(self.frag_off) == S + 1):
+            raise ValueError("BatchOutcome: per-spectrum arrays of different lengths")
+        if int(self.pos_off[-1]) != len(self.skeleton) or \
+                any(len(getattr(self, k)) != int(self.frag_off[-1]) for k in self.FRAGMENT_FIELDS):
+            raise ValueError("BatchOutcome: dense arrays do not match their offsets")
+
+    def __len__(self):
+        return len(self.default)
+
+    @classmethod
+    def array_fields(cls):
+        return tuple(cls._DTYPES)
+
+    def equals(self, other, ignore=()):
+        """Field by field (arrays exactly), apart from the fields in `ignore`."""
+        for k in self.array_fields():
+            if k not in ignore and not np.array_equal(getattr(self, k), getattr(other, k)):
+                return False
+        return all(k in ignore or getattr(self, k) == getattr(other, k) for k in ("breakage_names", "row_names"))
+
+    def _names_of(self, mask):
+        m0, m1 = int(mask[0]), int(mask[1])
+        return [self.row_names[r] for r in range(1, len(self.row_names))
+                if ((m0 >> r) & 1 if r < 64 else (m1 >> (r - 64)) & 1)]
+
+    def skeleton_seq(self, g):
+        """Spectrum g's skeleton sequence: per position the sorted names."""
+        return [sorted(self._names_of(p)) for p in self.skeleton[int(self.pos_off[g]):int(self.pos_off[g + 1])]]
+
+    def fragments(self, g):
+        """Spectrum g's fragments as predict's frame at its MILP stages."""
+        from .frame import Frame
+
+        s = slice(int(self.frag_off[g]), int(self.frag_off[g + 1]))
+        code = self.frag_code[s]
+        return Frame({"index": self.frag_index[s].tolist(), "standard_unit_mass": self.frag_su[s].tolist(),
+                      "observed_mass": self.frag_obs[s].tolist(),
+                      "breakage": [self.breakage_names[c & 3] for c in code.tolist()],
+                      "is_singleton": ((code >> 4) & 1).astype(bool).tolist(),
+                      "min_end": self.frag_min_end[s].tolist(), "max_end": self.frag_max_end[s].tolist()})
+
+    def alphabet_masses(self, g):
+        """The integer masses of spectrum g's alphabet after the skeleton-based
+        reduction, as [m.mass for m in dp_table.masses] (0 first)."""
+        m0, m1 = int(self.alpha[g, 0]), int(self.alpha[g, 1])
+        return [0] + [int(self.row_mass[r]) for r in range(1, len(self.row_mass))
+                      if ((m0 >> r) & 1 if r < 64 else (m1 >> (r - 64)) & 1)]
+
+    def take(self, idx):
+        """The outcome of spectra idx, in that order."""
+        idx = np.asarray(idx, dtype=np.int64)
+        p_src, p_off = _segments(self.pos_off, idx)
+        f_src, f_off = _segments(self.frag_off, idx)
+        kw = {k: getattr(self, k)[idx] for k in self.SPECTRUM_FIELDS}
+        kw.update({k: getattr(self, k)[p_src] for k in self.POSITION_FIELDS})
+        kw.update({k: getattr(self, k)[f_src] for k in self.FRAGMENT_FIELDS})
+        return BatchOutcome(pos_off=p_off, frag_off=f_off, breakage_names=self.breakage_names,
+                            row_names=self.row_names, row_mass=self.row_mass, **kw)
+
+    @classmethod
+    def concat(cls, outcomes):
+        """Several outcomes' spectra one after the other (ranks' shards in
+        rank order; the pieces of a splice), offsets rebased."""
+        outcomes = list(outcomes)
+        if not outcomes:
+            raise ValueError("BatchOutcome.concat: nothing to concatenate")
+        first = outcomes[0]
+        for o in outcomes[1:]:
+            if o.breakage_names != first.breakage_names or o.row_names != first.row_names or \
+                    not np.array_equal(o.row_mass, first.row_mass):
+                raise ValueError("BatchOutcome.concat: outcomes of different tables or breakage dicts")
+        kw = {k: np.concatenate([getattr(o, k) for o in outcomes])
+              for k in cls.SPECTRUM_FIELDS + cls.POSITION_FIELDS + cls.FRAGMENT_FIELDS}
+        for k in ("pos_off", "frag_off"):
+            base = np.concatenate([[0], np.cumsum([int(getattr(o, k)[-1]) for o in outcomes])]).astype(np.int64)
+            kw[k] = np.concatenate([getattr(o, k)[:-1] + b for o, b in zip(outcomes, base)] + [base[-1:]])
+        return cls(breakage_names=first.breakage_names, row_names=first.row_names, row_mass=first.row_mass, **kw)
+
+    def pack(self):
+        """One flat uint8 array (magic word, sizes, then every array's bytes):
+        what parallel.Gatherer ships from a rank."""
+        names = "\n".join(self.breakage_names).encode() + b"\0" + "\n".join(self.row_names).encode()
+        parts = [np.ascontiguousarray(getattr(self, k)).reshape(-1).view(np.uint8) for k in self.array_fields()]
+        parts.append(np.frombuffer(names, dtype=np.uint8))
+        head = np.array([HANDOFF_MAGIC, len(self), int(self.pos_off[-1]), int(self.frag_off[-1]), len(self.row_mass),
+                         len(names), 0, 0], dtype=np.int64)
+        head[6] = 64 + sum(p.nbytes for p in parts)
+        return np.concatenate([head.view(np.uint8)] + parts)
+
+    @classmethod
+    def unpack(cls, buf):
+        """pack()'s bytes -> BatchOutcome; ValueError for another buffer, a
+        truncated or an over-long one."""
+        b = np.ascontiguousarray(np.asarray(buf), dtype=np.uint8).reshape(-1)
+        if len(b) < 64:
+            raise ValueError("not a batch outcome buffer (shorter than its header)")
+        head = b[:64].copy().view(np.int64)
+        if int(head[0]) != HANDOFF_MAGIC:
+            raise ValueError("not a batch outcome buffer (magic word)")
+        S, n_pos, n_frag, n_rows, n_names, total = (int(x) for x in head[1:7])
+        if min(S, n_pos, n_frag, n_rows, n_names) < 0 or total != len(b):
+            raise ValueError("batch outcome buffer size mismatch")
+        counts = {"alpha": 2 * S, "pos_off": S + 1, "frag_off": S + 1, "skeleton": 2 * n_pos, "row_mass": n_rows}
+        counts.update({k: S for k in ("default", "route", "reason", "seq_len")})
+        counts.update({k: n_frag for k in cls.FRAGMENT_FIELDS})
+        o = 64
+        kw = {}
+        for k in cls.array_fields():
+            nb = np.dtype(cls._DTYPES[k]).itemsize * counts[k]
+            if o + nb > len(b):
+                raise ValueError("batch outcome buffer size mismatch")
+            kw[k] = b[o:o + nb].copy().view(cls._DTYPES[k])
+            o += nb
+        if o + n_names != len(b):
+            raise ValueError("batch outcome buffer size mismatch")
+        brk, _, rown = b[o:].tobytes().partition(b"\0")
+        return cls(breakage_names=brk.decode().split("\n") if brk else [],
+                   row_names=rown.decode().split("\n") if n_rows else [], **kw)
+
+
+def _empty_outcome(dp_table, names, S, route=ROUTE_DEVICE):
+    z = np.zeros
+    return BatchOutcome(default=np.ones(S, bool), route=np.full(S, route, np.uint8), reason=z(S, np.uint8),
+                        alpha=z((S, 2), np.uint64), seq_len=z(S, np.int32), pos_off=z(S + 1, np.int64),
+                        skeleton=z((0, 2), np.uint64), frag_off=z(S + 1, np.int64), frag_index=z(0, np.int32),
+                        frag_code=z(0, np.uint8), frag_su=z(0), frag_obs=z(0), frag_min_end=z(0, np.int32),
+                        frag_max_end=z(0, np.int32), breakage_names=names, row_names=_row_names(dp_table),
+                        row_mass=[m.mass for m in dp_table.masses])
+
+
+def mirror_outcome(dp_table, obs, su_mass, seq_mass, max_len, breakage_dict, intensity=None, intensity_cutoff=0.5e6,
+                   mass_cutoff=50000, explanation_masses=None, reason=0):
+    """One spectrum through the host mirror -- classify_fragments and
+    Predictor.predict_skeleton_stage on a DynamicProgrammingTable of its own
+    (its SequenceInformation from max_len, su_mass, seq_mass and dp_table's
+    modification rate; closed afterwards) -- as a one-spectrum BatchOutcome on
+    dp_table's rows.  The mirror has none of the device engines' limits."""
+    from .fragment_classification import classify_fragments
+    from .frame import Frame
+    from .mass_explanation import MASS_NAMES
+    from .mass_table import DynamicProgrammingTable, SequenceInformation
+    from .masses import EXPLANATION_MASSES
+    from .prediction import Predictor
+
+    em = EXPLANATION_MASSES if explanation_masses is None else explanation_masses
+    names = [breakage_dict[w][0] for w in breakage_dict]
+    out = _empty_outcome(dp_table, names, 1, ROUTE_MIRROR)
+    out.reason[0] = reason
+    seq = SequenceInformation(max_len=int(max_len), su_mass=float(su_mass), obs_mass=float(seq_mass),
+                              modification_rate=dp_table.seq.modification_rate)
+    dp = DynamicProgrammingTable(em, compression_rate=dp_table.compression_per_cell, tolerance=dp_table.tolerance,
+                                 precision=dp_table.precision, seq=seq, engine=dp_table._engine)
+    try:
+        cols = {"observed_mass": [float(x) for x in obs]}
+        if intensity is not None:
+            cols["intensity"] = [float(x) for x in intensity]
+        fr = classify_fragments(Frame(cols), dp, breakage_dict, intensity_cutoff=intensity_cutoff,
+                                mass_cutoff=mass_cutoff)
+        res = Predictor(dp, em).predict_skeleton_stage(fr)
+        kept = [m.mass for m in dp.masses[1:]]
+    finally:
+        dp.close()
+    if res is None:
+        return out
+    skeleton_seq, frags = res
+    row_of_mass = {m.mass: r for r, m in enumerate(dp_table.masses) if r}
+    row_of_name = {n: r for r, m in enumerate(dp_table.masses) if r for n in MASS_NAMES[m.mass]}
+
+    def mask(rows):
+        m = [0, 0]
+        for r in rows:
+            m[r >> 6] |= 1 << (r & 63)
+        return m
+
+    cols = frags.to_dict() if hasattr(frags, "to_dict") else {c: frags.get_column(c).to_list() for c in frags.columns}
+    brk = cols["breakage"]
+    code = [names.index(b) | ("START" in b) << 2 | ("END" in b) << 3 | bool(s) << 4
+            for b, s in zip(brk, cols["is_singleton"])]
+    n = len(brk)
+    return BatchOutcome(default=[False], route=[ROUTE_MIRROR], reason=[reason],
+                        alpha=np.array([mask(row_of_mass[m] for m in kept)], dtype=np.uint64),
+                        seq_len=[len(skeleton_seq)], pos_off=[0, len(skeleton_seq)],
+                        skeleton=np.array([mask(row_of_name[x] for x in p) for p in skeleton_seq],
+                                          dtype=np.uint64).reshape(-1, 2),
+                        frag_off=[0, n], frag_index=cols["index"], frag_code=code,
+                        frag_su=cols["standard_unit_mass"], frag_obs=cols["observed_mass"],
+                        frag_min_end=cols["min_end"], frag_max_end=cols["max_end"], breakage_names=names,
+                        row_names=out.row_names, row_mass=out.row_mass)
+
+
+def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=None, intensity=None,
+              intensity_cutoff=0.5e6, mass_cutoff=50000, limits=DeviceLimits(), fallback="mirror", name_hash=None,
+              trim=True, explanation_masses=None, record=None):
+    """These spectra -> what Predictor.predict holds when it reaches its MILP
+    stages (prediction.py:63-103), as a BatchOutcome: the six device stages
+    (classify_device, fixpoint_device, bins_device, skeleton_device,
+    length_device, post_skeleton_device) with `limits`' capacities, the two
+    hand-off calls (handoff_device), one download per output array.
+    obs / offsets: every spectrum's peaks (spectrum g: obs[offsets[g]:
+    offsets[g + 1]]; intensity likewise); su_seq / seq_mass [S] the
+    SequenceInformation masses; max_len [S] (None: pipeline.max_len_of over
+    explanation_masses' integer masses, cli.py:158-170); name_hash as
+    skeleton_device's; trim as length_device's.
+
+    A spectrum outside an engine limit does not fail or starve the batch: one
+    over limits.max_peaks or limits.max_len is taken out before stage 1, one
+    with a side whose walk ends WALK_LIMIT / WALK_SUSPENDED / WALK_ROUNDS /
+    WALK_MISSING after stage 4, one whose length bound is SST_ABORTED after
+    stage 5.  fallback="mirror": each of them runs the host mirror
+    (mirror_outcome) and its result is spliced in at its position (route 1,
+    reason the limit's REASON_* bit); fallback="raise": EngineError naming the
+    spectra and the reasons.  The mirror's explanation lists follow this
+    interpreter's set order (its str hashes), the device walk name_hash's: a
+    sharded run that passes rank 0's hashes runs its ranks under one
+    PYTHONHASHSEED so that routed spectra follow the same order.
+
+    The stages' batch-level error bits other than the peak count (ERR_BITS: a
+    window outside the pair class, an explanation dict too large for the LDS
+    hash, ...) still raise EngineError for the whole batch: the kernels report
+    them as one word per batch, and per-spectrum bits would change them.
+
+    record: a dict that receives diagnostics (walk_status [2 S], lb_status,
+    replay_nodes, jaccard_status of the spectra the device ran, device_index
+    their positions in the batch)."""
+    from .masses import EXPLANATION_MASSES, TOLERANCE
+    from .pipeline import max_len_of
+
+    if fallback not in ("mirror", "raise"):
+        raise ValueError(f"run_batch: fallback {fallback!r}")
+    em = EXPLANATION_MASSES if explanation_masses is None else explanation_masses
+    obs = np.ascontiguousarray(obs, dtype=np.float64)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    S = len(offsets) - 1
+    su_seq = np.ascontiguousarray(np.broadcast_to(np.asarray(su_seq, dtype=np.float64), (S,)))
+    seq_mass = np.ascontiguousarray(np.broadcast_to(np.asarray(seq_mass, dtype=np.float64), (S,)))
+    inten = None if intensity is None else np.ascontiguousarray(intensity, dtype=np.float64)
+    if max_len is None:
+        max_len = max_len_of(su_seq, TOLERANCE, min(em.get_column("tolerated_integer_masses").to_list()))
+    max_len = np.ascontiguousarray(np.broadcast_to(np.asarray(max_len, dtype=np.int64), (S,)))
+    names = [breakage_dict[w][0] for w in breakage_dict]
+    reason = np.zeros(S, np.uint8)
+    peaks = np.diff(offsets)
+    reason[peaks > limits.max_peaks] |= REASON_PEAKS
+    reason[max_len > limits.max_len] |= REASON_MAX_LEN
+
+    def refuse():
+        bad = np.flatnonzero(reason)
+        if fallback == "raise" and len(bad):
+            what = "; ".join(f"spectrum {int(g)}: " + ", ".join(v for k, v in REASON_NAMES.items() if reason[g] & k)
+                             for g in bad[:32])
+            raise _native.EngineError(f"device pipeline: {len(bad)} spectra outside the engine limits ({what}"
+                                      + (", ..." if len(bad) > 32 else "") + ")")
+
+    refuse()
+    d_idx = np.flatnonzero(reason == 0)  # the spectra the device runs
+    dev_out = _empty_outcome(dp_table, names, len(d_idx))
+    if len(d_idx):
+        cut = np.concatenate([[0], np.cumsum(peaks[d_idx])]).astype(np.int64)
+        if len(d_idx) == S:
+            d_obs, d_int = obs, inten
+        else:
+            src, _ = _segments(offsets, d_idx)
+            d_obs, d_int = obs[src], None if inten is None else inten[src]
+        ml = max_len[d_idx]
+        rows = classify_device(dp_table, d_obs, cut, su_seq[d_idx], breakage_dict, intensity=d_int,
+                               intensity_cutoff=intensity_cutoff, mass_cutoff=mass_cutoff)
+        fx = fixpoint_device(dp_table, rows, ml)
+        bins = bins_device(dp_table, rows, fx.alpha, max_len=ml)
+        sk = skeleton_device(dp_table, rows, fx.alpha, ml, bins=bins, caps=tuple(limits.walk_caps),
+                             big_caps=tuple(limits.walk_big_caps), max_rounds=limits.walk_max_rounds,
+                             name_hash=name_hash)
+        side = np.isin(sk.status, (_native.WALK_LIMIT, _native.WALK_SUSPENDED, _native.WALK_ROUNDS,
+                                   _native.WALK_MISSING)).reshape(-1, 2)
+        r_dev = np.where(side.any(axis=1), REASON_WALK, 0).astype(np.uint8)
+        reason[d_idx] |= r_dev
+        refuse()
+    if len(d_idx) and (r_dev == 0).any():  # (else: every spectrum goes to the mirror)
+        ln = length_device(dp_table, sk, bins.alpha_dev, su_seq[d_idx], seq_mass[d_idx],
+                           spectra=np.flatnonzero(r_dev == 0) if r_dev.any() else None,
+                           frontier_workspace=int(limits.frontier_workspace), trim=trim)
+        r_dev[(ln.lb_status == _native.SST_ABORTED) & (r_dev == 0)] |= REASON_FRONTIER
+        reason[d_idx] |= r_dev
+        refuse()
+        post = post_skeleton_device(dp_table, rows, sk, ln)
+        act = (np.asarray(post.active[:len(d_idx)]) != 0) & (r_dev == 0)
+        h = handoff_device(dp_table, rows, ln, post, active=act)
+        if record is not None:
+            record.update(device_index=d_idx, walk_status=sk.status.copy(), lb_status=ln.lb_status.copy(),
+                          replay_nodes=None if ln.replay_nodes is None else np.asarray(ln.replay_nodes).copy(),
+                          jaccard_status=ln.status.copy(), handoff_bytes=h["bytes"])
+        dev_out = BatchOutcome(default=~act, route=np.zeros(len(d_idx), np.uint8), reason=np.zeros(len(d_idx), np.uint8),
+                               alpha=np.where(act[:, None], post.alpha[:len(d_idx)], np.uint64(0)),
+                               seq_len=np.where(act, ln.seq_len[:len(d_idx)], 0), pos_off=h["pos_off"],
+                               skeleton=h["skeleton"], frag_off=h["frag_off"], frag_index=h["index"],
+                               frag_code=h["code"], frag_su=h["su"], frag_obs=h["obs"], frag_min_end=h["min_end"],
+                               frag_max_end=h["max_end"], breakage_names=names, row_names=dev_out.row_names,
+                               row_mass=dev_out.row_mass)
+    m_idx = np.flatnonzero(reason)
+    if not len(m_idx):
+        return dev_out
+    mirrored = [mirror_outcome(dp_table, obs[offsets[g]:offsets[g + 1]], su_seq[g], seq_mass[g], max_len[g],
+                               breakage_dict, None if inten is None else inten[offsets[g]:offsets[g + 1]],
+                               intensity_cutoff, mass_cutoff, em, int(reason[g])) for g in m_idx.tolist()]
+    both = BatchOutcome.concat([dev_out] + mirrored)
+    where = np.empty(S, np.int64)  # spectrum g's place in `both`: its device slot, or its mirror run
+    where[d_idx] = np.arange(len(d_idx))
+    where[m_idx] = len(d_idx) + np.arange(len(m_idx))
+    return both.take(where)

@@ -49,7 +49,7 @@ k_pairs_alpha).  Every stage reports its event-timed kernel time and the
 GPU-busy share of its wall time.
 
 Usage: python tools/pipeline_bench.py [--spectra 100000] [--seed 7] [--host-driven]
-       [--backend nccl|gloo] [--dump-outcomes DIR] [--as-rank R]
+       [--backend nccl|gloo] [--dump-outcomes DIR] [--as-rank R] [--handoff [--handoff-repeats 3]]
 """
 import argparse
 import json
@@ -216,6 +216,61 @@ def stages_cpu_baseline(dp, rows, fx, sk, args, data_rank, budget_s):
     return res
 
 
+def handoff_timings(pd, dp, rows, ln, post, repeats):
+    """--handoff: seconds and bytes moved of the dense hand-off
+    (pipeline_device.handoff_device: count, emit, one download per output
+    array) and of getting the same data the way to_classified does --
+    downloading rows.su / obs / meta, post.alive / min_end / max_end and the
+    combined skeleton whole and compacting them with numpy.  One untimed run
+    of each first; both must deliver the same arrays."""
+    import torch
+
+    dev = rows.su.device
+    S = len(ln.seq_len)
+
+    def whole_arrays():
+        off = rows.peak_off.cpu().numpy()
+        cnt = rows.rows.cpu().numpy().astype(np.int64)[:S]
+        host = [t.cpu().numpy() for t in (rows.su, rows.obs, rows.meta, post.alive, post.min_end, post.max_end,
+                                          ln.comb)]
+        su, ob, meta, alive, lo, hi, comb = host
+        moved = off.nbytes + rows.rows.numel() * 4 + sum(a.nbytes for a in host)
+        act = np.asarray(post.active[:S]) != 0
+        cnt = np.where(act, cnt, 0)
+        spec = np.repeat(np.arange(S), cnt)
+        local = np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+        slot = 4 * off[:-1][spec] + local
+        keep = alive[slot] != 0
+        slot, spec, local = slot[keep], spec[keep], local[keep]
+        n_pos = np.where(act, ln.seq_len[:S], 0).astype(np.int64)
+        pos = np.repeat(np.asarray(ln.comb_off[:S], dtype=np.int64), n_pos) + \
+            (np.arange(int(n_pos.sum())) - np.repeat(np.cumsum(n_pos) - n_pos, n_pos))
+        return {"frag_off": np.searchsorted(spec, np.arange(S + 1)), "pos_off": np.concatenate([[0], np.cumsum(n_pos)]),
+                "index": local.astype(np.int32), "code": (meta[slot] & 0x1f).astype(np.uint8), "su": su[slot],
+                "obs": ob[slot], "min_end": lo[slot], "max_end": hi[slot],
+                "skeleton": comb[pos].view(np.uint64), "bytes": int(moved)}
+
+    def timed(fn):
+        out, ts = fn(), []  # untimed
+        for _ in range(repeats):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            out = fn()
+            ts.append(time.perf_counter() - t0)
+        return out, ts
+
+    a, ta = timed(lambda: pd.handoff_device(dp, rows, ln, post))
+    b, tb = timed(whole_arrays)
+    same = all(np.array_equal(a[k], b[k]) for k in a if k != "bytes")
+    return {"spectra": S, "row_slots": int(rows.su.numel()), "fragments": int(a["frag_off"][-1]),
+            "positions": int(a["pos_off"][-1]), "repeats": repeats, "same_arrays": bool(same),
+            "kernels": {"s": ta, "s_min": min(ta), "s_median": float(np.median(ta)), "bytes": a["bytes"],
+                        "path": "sst_handoff_count_device + sst_handoff_emit_device + one download per output array"},
+            "whole_arrays": {"s": tb, "s_min": min(tb), "s_median": float(np.median(tb)), "bytes": b["bytes"],
+                             "path": "rows.su/obs/meta, post.alive/min_end/max_end and the combined skeleton "
+                                     "downloaded whole, compacted with numpy"}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--spectra", type=int, default=100000, help="spectra per GPU")
@@ -242,6 +297,13 @@ def main():
     ap.add_argument("--name-hashes", default=None,
                     help="a .npy of the rows' name hashes (the skeleton walk's set order) to use instead of this "
                          "interpreter's; a multi-rank run always uses rank 0's (saved with --dump-outcomes)")
+    ap.add_argument("--handoff", action="store_true",
+                    help="after the timed stages, also time the dense hand-off (the two sst_handoff_*_device calls "
+                         "plus one download per output array) and, for the same data, downloading the row-slot "
+                         "arrays whole and compacting them with numpy (to_classified's way); reported under "
+                         "\"handoff\", outside the stages' total")
+    ap.add_argument("--handoff-repeats", type=int, default=3, help="--handoff: timed repeats of each way (after one "
+                                                                   "untimed run)")
     ap.add_argument("--as-rank", type=int, default=None,
                     help="single process: generate the spectra rank R of a multi-rank run would get")
     args = ap.parse_args()
@@ -502,6 +564,10 @@ def main():
         stages["gather"] = {"s": tmax(time.perf_counter() - t0), "bytes_per_rank": sizes, "kernels": kernels(),
                             "path": "pack_outcomes + one agreed-size gather to rank 0"
                                     + (f" ({'RCCL' if args.backend == 'nccl' else 'gloo'})" if dist else " (local)")}
+    handoff = None
+    if rows is not None and args.handoff:
+        engine.profile(False)  # (the hand-off is timed by the wall clock alone, outside the stages)
+        handoff = handoff_timings(pd, dp, rows, ln, post, max(1, args.handoff_repeats))
     engine.profile(False)
     engine.trim()  # the frontier's workspace back to the allocator (sst_ctx_trim), after the timed stages
     if not args.host_driven:
@@ -544,6 +610,7 @@ def main():
                     o)
     if rank == 0:
         print(json.dumps({
+            **({"handoff": handoff} if handoff is not None else {}),
             "workload": "config5: the prediction pipeline's explanation stages (classify_fragments, the "
                         "filter_by_explanation fixpoint with per-spectrum alphabets, skeleton bin queries, the "
                         "skeleton walk, both length bounds and the Jaccard length on the skeleton alphabets; "
