@@ -2,7 +2,10 @@
 // side of libsstgpu.so.  Not part of the public ABI (see include/sst.h).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "sst.h"
 
@@ -248,6 +251,33 @@ struct ValidArgs {  // is_valid_mass batch
 struct PeakShifts {  // breakage weight x precision per output block (k_is_valid_peaks)
   double shift[4];
 };
+
+// Kernel arguments of the pair scan and the fused step, each passed as ONE
+// by-value struct: it then starts at byte 0 of the kernarg segment and every
+// member's kernarg offset is its offsetof().  The scan keeps only what its
+// tile loop reads as kernel-entry values; the end phase (and the rare blocks
+// inside the loop) load their members from the kernarg segment again
+// (scan_karg, sst_kernels.hip), so that they hold no SGPRs across the loop.
+struct ScanArgs {
+  TableArgs t;
+  QueryArgs q;
+  OutArgs out;
+};
+struct StepArgs {
+  ScanArgs s;  // first: the scan addresses it at the same offsets in both kernels
+  ValidArgs v;
+  PeakShifts sh;
+  uint32_t a7_blocks;
+};
+static_assert(std::is_standard_layout<ScanArgs>::value && std::is_trivially_copyable<ScanArgs>::value,
+              "ScanArgs members are addressed by offsetof() in the kernarg segment");
+static_assert(std::is_standard_layout<StepArgs>::value && std::is_trivially_copyable<StepArgs>::value,
+              "StepArgs members are addressed by offsetof() in the kernarg segment");
+static_assert(offsetof(ScanArgs, t) == 0 && offsetof(ScanArgs, q) == sizeof(TableArgs) &&
+                  offsetof(ScanArgs, out) == sizeof(TableArgs) + sizeof(QueryArgs) && offsetof(StepArgs, s) == 0,
+              "no padding between the scan's argument blocks; StepArgs starts with them");
+static_assert(alignof(ScanArgs) == 8 && alignof(StepArgs) == 8 && sizeof(StepArgs) <= 4096,
+              "8-B aligned members only (scalar loads), within the kernarg segment's limit");
 
 struct LBArgs {
   const double* su;

@@ -1617,6 +1617,9 @@ struct PairLds {
   uint32_t base;
   int shift;
 };
+__device__ __forceinline__ PairLds scan_pair_lds(const uint32_t* img, int n_pairs, uint32_t base, int shift) {
+  return PairLds{img, img + n_pairs + 2, img + 2 * (n_pairs + 2), base, shift};
+}
 __device__ __forceinline__ uint32_t pair_walk(const PairLds& p, uint32_t a, uint32_t hi, uint32_t& first,
                                               uint32_t& bytes) {
   const uint32_t rel = a > p.base ? a - p.base : 0u;
@@ -1745,6 +1748,8 @@ __device__ __forceinline__ uint64_t ctl_read(uint64_t* ctl, int k) {  // counter
 // for the next tile's inputs be exact: the in-order counter then never makes
 // a tile wait for the stores of the tile just before it.
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+constexpr int kImgPieces = 3;  // 16-B pieces of the pair image per scan lane (kMaxPairLds / 16 / kScanWG, rounded up)
 constexpr uint32_t kBufSkip = 0x80000000u;
 constexpr int kPreChunks = 4;  // hit-record chunks a scan wave prepares before its look-back wait  // an offset past every buffer the scan addresses
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* base, uint32_t bytes) {
@@ -1777,21 +1782,63 @@ __device__ __forceinline__ uint32_t pair_bytes(const PairLds& p, uint32_t first,
 // placed by a decoupled look-back over the workgroups' totals (the last
 // workgroup writes the header); otherwise its payload region and 8-B records
 // {query, count | bytes << 16} for k_result_pack.
+//
+// Arguments: the kernels pass ScanArgs / StepArgs by value, so `a` holds the
+// kernel-entry values and the same bytes lie at offset 0 of the kernarg
+// segment.  The tile loop reads entry values only, and only the members its
+// hot path needs; everything else -- the end phase after the loop, and inside
+// the loop the rare routing block and the quantisation fallback -- loads its
+// members from the kernarg segment where it runs (SCAN_KARG: scalar loads at
+// offsetof() behind a compiler barrier, so they are not hoisted above the
+// loop).  Held across the loop instead, those members spill: the loop then
+// re-reads them lane by lane from a spill VGPR on every tile.
+typedef const __attribute__((address_space(4))) char* KargPtr;
+__device__ __forceinline__ KargPtr scan_karg() {
+  KargPtr p = (KargPtr)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));  // opaque from here on: loads through p stay where they are written
+  return p;
+}
+template <typename T>
+__device__ __forceinline__ T karg_load(KargPtr p, size_t off) {
+  static_assert(std::is_trivially_copyable<T>::value, "kernarg members are plain data");
+  T v;  // (the typed source gives the copy T's alignment: scalar loads need 4 B)
+  __builtin_memcpy(&v, (const __attribute__((address_space(4))) T*)(p + off), sizeof(T));
+  return v;
+}
+#define SCAN_KARG(p, member) \
+  karg_load<std::remove_cv_t<decltype(((ScanArgs*)nullptr)->member)>>(p, offsetof(ScanArgs, member))
+
 template <bool THR, bool MODS>
-__device__ __forceinline__ void explain_scan_wg(const TableArgs& t, const QueryArgs& q, const OutArgs& out,
-                                                const uint32_t bid, const uint32_t nbid) {
+__device__ __forceinline__ void scan_end_phase(uint32_t bid, uint32_t nbid, uint32_t w_in, int lane, uint32_t n_hit,
+                                               uint32_t n_staged, uint32_t n_work, uint32_t st_q,
+                                               uint32_t st_payload);
+
+template <bool THR, bool MODS>
+__device__ __forceinline__ void explain_scan_wg(const ScanArgs& a, const uint32_t bid, const uint32_t nbid) {
+  const TableArgs& t = a.t;
+  const QueryArgs& q = a.q;
+  const OutArgs& out = a.out;
   extern __shared__ uint32_t lds_pair_img[];
   if (bid == 0) {
     if (threadIdx.x < (unsigned)out.ctl_words) out.ctl_next[threadIdx.x] = 0;
     for (uint32_t k = threadIdx.x; k < nbid; k += blockDim.x) out.agg_next[k] = 0;
   }
   const int n_img = 2 * (t.n_pairs + 2) + t.n_buckets;
-  // 16-B copies (the image is padded to 16 B; 4-B copies: scan +2.5 us)
-  for (int k = threadIdx.x; k < ((n_img + 3) >> 2); k += blockDim.x)
-    ((uint4*)lds_pair_img)[k] = ((const uint4*)t.pair_data)[k];
-  __syncthreads();
-  const PairLds pl{lds_pair_img, lds_pair_img + t.n_pairs + 2, lds_pair_img + 2 * (t.n_pairs + 2), t.pair_base,
-                   t.pair_shift};
+  // The image's staging loads are issued first (16-B pieces: the image is
+  // padded to 16 B; 4-B copies: scan +2.5 us; a piece past its end is dropped
+  // by the buffer's range check), then the first two tiles' input prefetches;
+  // the LDS writes and the barrier follow those, so the inputs' HBM round
+  // trip runs under the staging instead of after it.  (The prefetches in
+  // FRONT of the staging loads: +1.6 us, the in-order vmcnt then makes the
+  // staging wait for HBM.)
+  static_assert(kMaxPairLds <= kImgPieces * kScanWG * 16, "the image is staged in kImgPieces pieces per lane");
+  const uint32_t n_img16 = (uint32_t)(n_img + 3) >> 2;
+  const __amdgpu_buffer_rsrc_t img_rsrc = buf_rsrc(t.pair_data, n_img16 * 16u);
+  u32x4 img[kImgPieces];
+#pragma unroll
+  for (int j = 0; j < kImgPieces; ++j)
+    img[j] = __builtin_amdgcn_raw_buffer_load_b128(img_rsrc, (threadIdx.x + j * kScanWG) * 16u, 0, 0);
+  const PairLds pl = scan_pair_lds(lds_pair_img, t.n_pairs, t.pair_base, t.pair_shift);
   const int lane = threadIdx.x & 63;
   // wave-uniform in SGPRs (the buffer resources below must be scalar)
   const uint32_t w_in = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1813,7 +1860,6 @@ __device__ __forceinline__ void explain_scan_wg(const TableArgs& t, const QueryA
   // slots during the tiles, copied to the class lists after them with one
   // atomic per class per workgroup -- atomics of every wave on the shared
   // class counters serialise (config 1: scan 80 -> 44 us without them)
-  uint32_t* const stage = out.stage + (uint64_t)wave * out.work_region;
   uint32_t n_staged = 0;  // wave-uniform (one SGPR in the tile loop: the per-class counts are taken after it)
   // Software pipeline, two tiles deep: a tile's inputs are loaded two tiles
   // ahead into one of two register sets that swap roles between the unrolled
@@ -1831,25 +1877,20 @@ __device__ __forceinline__ void explain_scan_wg(const TableArgs& t, const QueryA
     const bool live = i < n;
     const double m_cur = m_in, t_cur = THR ? t_in : q.tol * m_in;
     double lof, hif;
-    quantise_lean(m_cur, t_cur, q.prec, q.rprec, lof, hif);
+    quantise_lean_fn(m_cur, t_cur, [] { return SCAN_KARG(scan_karg(), q.prec); }, q.rprec, lof, hif);
     const bool nonempty = live && lof <= hif;
     const bool oot = nonempty && !(hif < limitf);  // mass_explanation.py:134-138 (NotImplementedError)
     const bool zero = nonempty && !oot && lof <= 0.0 && hif >= 0.0;  // v == 0 -> [[]] (:130-131)
     const double af = __builtin_fmax(lof, 1.0);
     const bool active = nonempty && !oot && af <= hif;
     const uint32_t a = active ? (uint32_t)af : 0u, hi = active ? (uint32_t)hif : 0u;
-    bool pair, never;
+    bool pair, a0ok = true;  // (never: the fast-path theorem, taken in the routing block, its only reader)
     if (MODS) {  // fast-path theorem per lane (budgets_never_bind on u32 values)
       const int A0 = clamp_budget(mm_cur);
-      const bool a0ok =
-          !t.any_mod || A0 >= kInfBudget || (uint64_t)hi < (uint64_t)(A0 + 1) * (uint64_t)t.w_min_mod;
+      a0ok = !t.any_mod || A0 >= kInfBudget || (uint64_t)hi < (uint64_t)(A0 + 1) * (uint64_t)t.w_min_mod;
       pair = active && a0ok && hi < t.pair_lim;
-      // per-query budgets: the fast-path limit of the query's caps
-      const uint32_t nl = q.qlen ? q.never_len[q.qlen[live ? i : n - 1]] : t.never_lim;
-      never = a0ok && hi < nl;
     } else {
       pair = active && hi < q.pair_hi_lim;
-      never = hi < q.never_hi_lim;
     }
     const bool work = active && !pair;  // routed below (bitset, depth, budgets)
     uint32_t first = 0, cnt = 0, bytes = 0;
@@ -1871,15 +1912,26 @@ __device__ __forceinline__ void explain_scan_wg(const TableArgs& t, const QueryA
       // (the class's role reads the window's bitset words itself: a window
       // without reachable values costs it one look; none here keeps the
       // tile loop free of scattered loads)
+      // (its arguments come from the kernarg segment here, not from registers held across every tile)
+      const KargPtr ka = scan_karg();
+      bool never;
+      if (MODS) {  // per-query budgets: the fast-path limit of the query's caps
+        const int32_t* const qlen = SCAN_KARG(ka, q.qlen);
+        const uint32_t nl = qlen ? SCAN_KARG(ka, q.never_len)[qlen[live ? i : n - 1]] : SCAN_KARG(ka, t.never_lim);
+        never = a0ok && hi < nl;
+      } else {
+        never = hi < SCAN_KARG(ka, q.never_hi_lim);
+      }
       int cls = -1;
       if (work) {
-        if (never && hi < t.shallow_hi) {
+        if (never && hi < SCAN_KARG(ka, t.shallow_hi)) {
           cls = kClassShallow;  // <= 3 items, budgets cannot bind: the SHALLOW role writes the result
         } else {
-          cls = never ? kClassDeep : (q.with_memo ? kClassExact : kClassNomemo);
-          out.status[i] = (int8_t)kStatusPending;
+          cls = never ? kClassDeep : (SCAN_KARG(ka, q.with_memo) ? kClassExact : kClassNomemo);
+          SCAN_KARG(ka, out.status)[i] = (int8_t)kStatusPending;
         }
       }
+      uint32_t* const stage = SCAN_KARG(ka, out.stage) + (uint64_t)wave * SCAN_KARG(ka, out.work_region);
       const uint64_t cb = __ballot(cls >= 0);
       if (cls >= 0) stage[n_staged + mbcnt(cb)] = i | ((uint32_t)cls << 30);
       n_staged += (uint32_t)__builtin_popcountll(cb);
@@ -1899,6 +1951,10 @@ __device__ __forceinline__ void explain_scan_wg(const TableArgs& t, const QueryA
   __builtin_amdgcn_raw_buffer_store_b8(0, st_rsrc, kBufSkip, 0, 0);
   __builtin_amdgcn_raw_buffer_store_b8(1, st_rsrc, kBufSkip + 64u, 0, 0);
   fetch(vw + n_waves, mB, tB, mmB);
+#pragma unroll
+  for (int j = 0; j < kImgPieces; ++j)
+    if (threadIdx.x + j * kScanWG < n_img16) ((u32x4*)lds_pair_img)[threadIdx.x + j * kScanWG] = img[j];
+  __syncthreads();
   for (uint32_t tile = vw; tile < ntiles; tile += 2 * n_waves) {
     step(tile, mA, tA, mmA);
     fetch(tile + 2 * n_waves, mA, tA, mmA);
@@ -1906,6 +1962,28 @@ __device__ __forceinline__ void explain_scan_wg(const TableArgs& t, const QueryA
     step(tile + n_waves, mB, tB, mmB);
     fetch(tile + 3 * n_waves, mB, tB, mmB);
   }
+  scan_end_phase<THR, MODS>(bid, nbid, w_in, lane, n_hit, n_staged, n_work, st_q, st_payload);
+}
+
+// The scan's end phase: everything a scan wave does after its tiles, from
+// its loop state and the arguments as the kernarg segment holds them.
+template <bool THR, bool MODS>
+__device__ __forceinline__ void scan_end_phase(const uint32_t bid, const uint32_t nbid, const uint32_t w_in,
+                                               const int lane, const uint32_t n_hit, const uint32_t n_staged,
+                                               const uint32_t n_work, const uint32_t st_q,
+                                               const uint32_t st_payload) {
+  extern __shared__ uint32_t lds_pair_img[];
+  const KargPtr ka = scan_karg();
+  const OutArgs out = SCAN_KARG(ka, out);  // (only the members read below are loaded)
+  struct {
+    int64_t n;
+    uint32_t cap32;
+  } const q{SCAN_KARG(ka, q.n), SCAN_KARG(ka, q.cap32)};
+  const PairLds pl = scan_pair_lds(lds_pair_img, SCAN_KARG(ka, t.n_pairs), SCAN_KARG(ka, t.pair_base),
+                                   SCAN_KARG(ka, t.pair_shift));
+  const uint32_t wave = bid * (kScanWG / 64) + w_in;
+  uint4* const wl = out.work + (uint64_t)wave * out.work_region;
+  uint32_t* const stage = out.stage + (uint64_t)wave * out.work_region;
   // ---- the wave's totals: hit records, payload bytes (16-B units per wave
   // piece of the payload)
   const uint32_t pay = wave_sum32(st_payload);
@@ -2088,8 +2166,8 @@ __device__ __forceinline__ void explain_scan_wg(const TableArgs& t, const QueryA
   }
 }
 template <bool THR, bool MODS>
-__global__ __launch_bounds__(kScanWG, 8) void k_explain_scan(TableArgs t, QueryArgs q, OutArgs out) {
-  explain_scan_wg<THR, MODS>(t, q, out, blockIdx.x, gridDim.x);
+__global__ __launch_bounds__(kScanWG, 8) void k_explain_scan(ScanArgs a) {
+  explain_scan_wg<THR, MODS>(a, blockIdx.x, gridDim.x);
 }
 // One launch for a step of both predicates (sst_step_device): the pair
 // scan's grid, then a7_blocks workgroups of is_valid over peaks x 4 breakage
@@ -2101,14 +2179,13 @@ __global__ __launch_bounds__(kScanWG, 8) void k_explain_scan(TableArgs t, QueryA
 // instead: 8 us slower per step; two scan workgroups per CU, is_valid only in
 // the scan's tail: 2 us slower; same-box A/Bs.)
 template <bool THR, bool MODS>
-__global__ __launch_bounds__(kScanWG, 8) void k_step(TableArgs t, QueryArgs q, OutArgs out, ValidArgs v, PeakShifts sh,
-                                                   uint32_t a7_blocks) {
-  const uint32_t n_scan = gridDim.x - a7_blocks;
+__global__ __launch_bounds__(kScanWG, 8) void k_step(StepArgs a) {
+  const uint32_t n_scan = gridDim.x - a.a7_blocks;
   if (blockIdx.x >= n_scan) {
-    is_valid_peak<4>(v, sh, (blockIdx.x - n_scan) * kScanWG + threadIdx.x);
+    is_valid_peak<4>(a.v, a.sh, (blockIdx.x - n_scan) * kScanWG + threadIdx.x);
     return;
   }
-  explain_scan_wg<THR, MODS>(t, q, out, blockIdx.x, n_scan);
+  explain_scan_wg<THR, MODS>(a.s, blockIdx.x, n_scan);
 }
 
 // the extent ceil((max(kept) * 35 + 1) / C) * C of query i's reduced table
@@ -3817,16 +3894,17 @@ hipError_t launch_explain_scan(const TableArgs& t, const QueryArgs& q, const Out
                                hipStream_t st) {
   if (q.n <= 0) return hipSuccess;
   const size_t dyn = scan_dyn_lds(t);
+  const ScanArgs a{t, q, o};
   if (!t.pairs_enabled)
     hipLaunchKernelGGL(k_bitset_scan, dim3(n_blocks), dim3(kScanWG), 0, st, t, q, o);
   else if (q.thr && q.max_mods)
-    hipLaunchKernelGGL((k_explain_scan<true, true>), dim3(n_blocks), dim3(kScanWG), dyn, st, t, q, o);
+    hipLaunchKernelGGL((k_explain_scan<true, true>), dim3(n_blocks), dim3(kScanWG), dyn, st, a);
   else if (q.thr)
-    hipLaunchKernelGGL((k_explain_scan<true, false>), dim3(n_blocks), dim3(kScanWG), dyn, st, t, q, o);
+    hipLaunchKernelGGL((k_explain_scan<true, false>), dim3(n_blocks), dim3(kScanWG), dyn, st, a);
   else if (q.max_mods)
-    hipLaunchKernelGGL((k_explain_scan<false, true>), dim3(n_blocks), dim3(kScanWG), dyn, st, t, q, o);
+    hipLaunchKernelGGL((k_explain_scan<false, true>), dim3(n_blocks), dim3(kScanWG), dyn, st, a);
   else
-    hipLaunchKernelGGL((k_explain_scan<false, false>), dim3(n_blocks), dim3(kScanWG), dyn, st, t, q, o);
+    hipLaunchKernelGGL((k_explain_scan<false, false>), dim3(n_blocks), dim3(kScanWG), dyn, st, a);
   return hipGetLastError();
 }
 hipError_t launch_step(const TableArgs& t, const QueryArgs& q, const OutArgs& o, int n_blocks, const double* obs,
@@ -3840,14 +3918,15 @@ hipError_t launch_step(const TableArgs& t, const QueryArgs& q, const OutArgs& o,
   for (int k = 0; k < 4; ++k) sh.shift[k] = shifts4[k];
   const uint32_t a7 = (uint32_t)((n_peaks + kScanWG - 1) / kScanWG);
   const dim3 grid(a7 + (uint32_t)n_blocks);
+  const StepArgs a{{t, q, o}, v, sh, a7};
   if (q.thr && q.max_mods)
-    hipLaunchKernelGGL((k_step<true, true>), grid, dim3(kScanWG), dyn, st, t, q, o, v, sh, a7);
+    hipLaunchKernelGGL((k_step<true, true>), grid, dim3(kScanWG), dyn, st, a);
   else if (q.thr)
-    hipLaunchKernelGGL((k_step<true, false>), grid, dim3(kScanWG), dyn, st, t, q, o, v, sh, a7);
+    hipLaunchKernelGGL((k_step<true, false>), grid, dim3(kScanWG), dyn, st, a);
   else if (q.max_mods)
-    hipLaunchKernelGGL((k_step<false, true>), grid, dim3(kScanWG), dyn, st, t, q, o, v, sh, a7);
+    hipLaunchKernelGGL((k_step<false, true>), grid, dim3(kScanWG), dyn, st, a);
   else
-    hipLaunchKernelGGL((k_step<false, false>), grid, dim3(kScanWG), dyn, st, t, q, o, v, sh, a7);
+    hipLaunchKernelGGL((k_step<false, false>), grid, dim3(kScanWG), dyn, st, a);
   return hipGetLastError();
 }
 hipError_t launch_explain_expand(const TableArgs& t, const QueryArgs& q, const OutArgs& o, int n_blocks,

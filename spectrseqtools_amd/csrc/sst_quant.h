@@ -52,9 +52,12 @@ __device__ __forceinline__ void quantise(double mass, double thr_abs, bool thr_n
 // correctly rounded division runs only when a product lies within 2^-50
 // (relative) of a point where rint / ceil change value, or is huge, so the
 // integers are exactly the reference's.  Straight-line except for that rare
-// fallback (the lean form of rint_quot / ceil_quot).
-__device__ __forceinline__ void quantise_lean(double m, double t, double prec, double rprec, double& lof,
-                                              double& hif) {
+// fallback (the lean form of rint_quot / ceil_quot).  prec_fn() gives prec
+// and is called on the fallback only (the pair scan loads it there instead of
+// holding it in registers across its tiles).
+template <typename PrecFn>
+__device__ __forceinline__ void quantise_lean_fn(double m, double t, PrecFn prec_fn, double rprec, double& lof,
+                                                 double& hif) {
   const double qm = m * rprec, qt = t * rprec;
   double rm = __builtin_rint(qm), ct = __builtin_ceil(qt);
   const double dm = qm - rm, dt = qt - __builtin_rint(qt);  // exact
@@ -62,11 +65,16 @@ __device__ __forceinline__ void quantise_lean(double m, double t, double prec, d
                     (0.5 - __builtin_fabs(dm) <= __builtin_fabs(qm) * 0x1p-50) |
                     (__builtin_fabs(dt) <= __builtin_fabs(qt) * 0x1p-50);
   if (__builtin_expect(slow, 0)) {
+    const double prec = prec_fn();
     rm = __builtin_rint(m / prec);
     ct = __builtin_ceil(t / prec);
   }
   lof = rm - ct;
   hif = rm + ct;
+}
+__device__ __forceinline__ void quantise_lean(double m, double t, double prec, double rprec, double& lof,
+                                              double& hif) {
+  quantise_lean_fn(m, t, [prec] { return prec; }, rprec, lof, hif);
 }
 
 // any bit of valid in [a, b] (a <= b, both < limit)
