@@ -316,6 +316,12 @@ int sst_result_hit_list(sst_result* r, void** d_hits, uint64_t* n_hits);
  * the status codes this is the whole pair-path result in ~4 B per hit and
  * no payload (parallel.wire_pack).  No reference equivalent. */
 int sst_result_pair_hits(sst_result* r, void** d_refs, uint64_t* n_pair_hits, uint64_t* pair_bytes, int* n_scan_wg);
+/* Hit records each scan wave of a device-path pass on this table keeps on
+ * chip (LDS) before it falls back to its worklist region in device memory:
+ * the most that leaves the scan's occupancy alone for the table's pair list,
+ * or what SST_SCAN_LDS_HITS forces (0 for tables without the list).  Results
+ * do not depend on it.  No reference equivalent. */
+int sst_table_scan_lds_hits(sst_table* t, uint32_t* per_wave);
 /* The table's pair list: payload record of entry e (u32: [k][row..] in its
  * low 2-3 bytes, the bytes sst_result_host's payload holds for that
  * candidate); *n = 0 for tables without the list.  recs may be NULL (size

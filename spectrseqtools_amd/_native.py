@@ -38,7 +38,7 @@ EXPORTS = (
     "sst_reach_rows_device", "sst_length_bounds_reach_device", "sst_jaccard_device", "sst_skeleton_alpha_device",
     "sst_dict_list_device", "sst_fix_finish_device", "sst_pipe_reserve_rows", "sst_reach_lowest_device",
     "sst_length_bounds_frontier_device", "sst_post_skeleton_device", "sst_ctx_trim", "sst_requery_merge_device",
-    "sst_handoff_count_device", "sst_handoff_emit_device",
+    "sst_handoff_count_device", "sst_handoff_emit_device", "sst_table_scan_lds_hits",
 )
 
 # kernel ids of sst_profile_read
@@ -239,6 +239,8 @@ def load_library(path=LIB_PATH):
     lib.sst_window_pairs.restype = _I64
     lib.sst_result_pair_hits.argtypes = [_P, _PP, ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_I)]
     lib.sst_result_pair_hits.restype = _I
+    lib.sst_table_scan_lds_hits.argtypes = [_P, ctypes.POINTER(ctypes.c_uint32)]
+    lib.sst_table_scan_lds_hits.restype = _I
     lib.sst_table_pair_records.argtypes = [_P, _P, _I64, ctypes.POINTER(_I64)]
     lib.sst_table_pair_records.restype = _I
     lib.sst_wire_pack.argtypes = [_P, _P, _I64, _P, _I64]
@@ -712,6 +714,13 @@ class DeviceTable:
         self.engine.check(self.engine._lib.sst_table_set_budgets(self.handle, _ptr(m), _ptr(c)),
                           "sst_table_set_budgets")
         self._budgets = key
+
+    def scan_lds_hits(self):
+        """Hit records per scan wave a device-path pass keeps in LDS (sst_table_scan_lds_hits)."""
+        k = ctypes.c_uint32()
+        self.engine.check(self.engine._lib.sst_table_scan_lds_hits(self.handle, ctypes.byref(k)),
+                          "sst_table_scan_lds_hits")
+        return int(k.value)
 
     def pair_records(self):
         """u32 payload record per pair-list entry (sst_table_pair_records);

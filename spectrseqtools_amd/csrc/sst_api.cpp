@@ -99,6 +99,7 @@ struct sst_ctx {
   uint32_t hash_cap = 0;
   int exact_blocks = 0;
   int n_cu = 256;       // compute units (persistent grid sizing)
+  size_t scan_dyn_max = 64 * 1024;  // dynamic LDS a scan launch may ask for (scan_allow_large_lds)
   int expand_blocks = 0;  // resident workgroups of k_explain_expand
   // measurement: hipEvents around launches on `stream`
   uint32_t prof = 0;  // kernel ids whose launches are bracketed by events
@@ -133,6 +134,7 @@ struct sst_table {
   uint64_t pair_key = 0;            // their FNV-1a (sst_wire_pack), computed on first use
   bool pair_key_set = false;
   int scan_blocks = 0;  // resident workgroups of k_explain_scan (depends on the LDS pair list size)
+  uint32_t lds_hits = 0;  // hit records per scan wave kept in LDS by a fused pass (set with scan_blocks)
   bool closure = false;  // built here from masses >= C: rows are true closures (layered fast paths valid)
   TableArgs args{};
 };
@@ -517,6 +519,7 @@ int sst_ctx_create(int device, sst_ctx** out) {
     return SST_E_HIP;
   }
   c->stream = c->own;
+  c->scan_dyn_max = sst::scan_allow_large_lds();
   *out = c;
   return SST_OK;
 }
@@ -1113,6 +1116,7 @@ int explain_pass(sst_table* t, sst_result* r, const double* d_mass, const double
   r->scan_hits = r->scan_bytes = 0;
   if (fused) {
     o.fused = 1;
+    o.lds_hits = t->lds_hits;  // (the unfused pass rewrites its records in place: all in the worklist region)
     o.pass_id = ++r->pack_seq;
 #ifdef SST_DIAG  // diagnostic builds only (make DIAG=1)
     static const char* dbg = getenv("SST_PACK_DBG");
@@ -1159,9 +1163,29 @@ int step_scan_wg_per_cu() {
   return v;
 }
 
+// Hit records a scan wave keeps in LDS (OutArgs::lds_hits): the most that
+// leaves the occupancy alone.  SST_SCAN_LDS_HITS forces a smaller capacity
+// (A/B and tests; 0: every record through the worklist region, as before the
+// LDS slots existed).
+uint32_t scan_lds_hits(size_t img_lds, size_t dyn_max) {
+  static const long forced = [] {
+    const char* e = getenv("SST_SCAN_LDS_HITS");
+    return e && *e ? atol(e) : -1L;
+  }();
+  const uint32_t most = scan_lds_hits_max(img_lds, dyn_max);
+  return forced >= 0 ? (uint32_t)std::min<long>(forced, (long)most) : most;
+}
+
+// the table's scan grid and LDS hit capacity (once per table: occupancy queries)
+void size_scan(sst_table* t) {
+  if (t->scan_blocks) return;
+  t->scan_blocks = t->ctx->n_cu * explain_scan_blocks_per_cu(scan_dyn_lds(t->args));
+  t->lds_hits = scan_lds_hits(scan_dyn_lds(t->args), t->ctx->scan_dyn_max);
+}
+
 int alloc_result(sst_table* t, int64_t n, sst_result** out, bool step = false) {
   sst_ctx* c = t->ctx;
-  if (t->scan_blocks == 0) t->scan_blocks = c->n_cu * explain_scan_blocks_per_cu(scan_dyn_lds(t->args));
+  size_scan(t);
   if (c->expand_blocks == 0) c->expand_blocks = c->n_cu * explain_expand_blocks_per_cu();
   sst_result* r = new sst_result();
   r->ctx = c;
@@ -1835,6 +1859,16 @@ int sst_result_pair_hits(sst_result* r, void** d_refs, uint64_t* n_pair_hits, ui
   if (n_pair_hits) *n_pair_hits = r->scan_hits;
   if (pair_bytes) *pair_bytes = r->scan_bytes;
   if (n_scan_wg) *n_scan_wg = r->rows_pass ? 0 : r->n_wg;  // 0: the hits come in query order
+  return SST_OK;
+}
+
+int sst_table_scan_lds_hits(sst_table* t, uint32_t* per_wave) {
+  if (!t || !per_wave) return SST_E_ARG;
+  sst_ctx* c = t->ctx;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  if (int rc = set_device(c)) return rc;
+  size_scan(t);
+  *per_wave = t->lds_hits;
   return SST_OK;
 }
 

@@ -177,7 +177,31 @@ struct OutArgs {
   uint64_t* hdr_host;  // host-mapped header (device address)
   uint64_t pass_id;
   int dbg;  // DIAGNOSTIC (SST_PACK_DBG): 1 no record copy, 2 no payload copy, 4 no look-back wait
+  // hit records a scan wave keeps in its LDS slot behind the pair image (fused
+  // passes only; 0: every record goes to the worklist region).  The launch's
+  // dynamic LDS is the image plus scan_hit_lds_bytes(lds_hits).
+  uint32_t lds_hits;
 };
+
+// A scan wave's LDS hit record: a u32 {first entry : 13, lane : 6, the tile's
+// ordinal within the wave : 13} and a u8 count, in two arrays per wave.  A
+// tile whose records do not fit these fields, or the slot, goes to the
+// worklist region, and so does every later tile of that wave (explain_scan_wg).
+// A wave's slot is one address: the u32 of record k lies 4 k bytes above it,
+// its count 1 + k bytes below (scan_hit_slot).
+constexpr int kHitFirstBits = 13, kHitLaneBits = 6, kHitOrdBits = 13;
+constexpr uint32_t kHitMaxCount = 255, kHitMaxOrd = (1u << kHitOrdBits) - 1u;
+static_assert(kMaxPairLds / 8 <= (1 << kHitFirstBits), "a pair-list entry index fits the LDS hit record");
+static_assert(kHitFirstBits + kHitLaneBits + kHitOrdBits == 32, "the LDS hit record's fields");
+constexpr size_t kCuLdsBytes = 160 * 1024;  // gfx950: LDS per CU
+constexpr uint32_t scan_hit_slot_bytes(uint32_t lds_hits) { return 4u * lds_hits + ((lds_hits + 3u) & ~3u); }
+inline size_t scan_hit_lds_bytes(uint32_t lds_hits) {
+  return (size_t)scan_hit_slot_bytes(lds_hits) * (kScanWG / 64);  // a multiple of 16
+}
+// byte offset behind the pair image of wave w_in's slot address
+__host__ __device__ inline uint32_t scan_hit_slot(uint32_t lds_hits, uint32_t w_in) {
+  return w_in * scan_hit_slot_bytes(lds_hits) + ((lds_hits + 3u) & ~3u);
+}
 
 // hit records: {query | flags, count (saturated to u32), word lo, word hi};
 // word = the byte offset of the query's candidates (SOME) or its exact
@@ -720,6 +744,8 @@ hipError_t launch_explain_expand(const TableArgs& t, const QueryArgs& q, const O
 int explain_scan_blocks_per_cu(size_t dyn_lds);
 int explain_expand_blocks_per_cu();
 size_t scan_dyn_lds(const TableArgs& t);
+size_t scan_allow_large_lds();  // once per context, before its first scan launch: the dynamic LDS a launch may ask for
+uint32_t scan_lds_hits_max(size_t img_lds, size_t dyn_max);  // OutArgs::lds_hits that keeps the scan's occupancy
 hipError_t launch_result_pack(const PackArgs& p, hipStream_t st);
 hipError_t launch_hits_to_arrays(const uint4* hits, uint64_t n_hits, const int8_t* status, uint64_t* count,
                                  uint64_t* offset, hipStream_t st);

@@ -1773,9 +1773,12 @@ __device__ __forceinline__ uint32_t pair_bytes(const PairLds& p, uint32_t first,
 // exact f64 integers, then u32 (a window inside the table lies in [0, limit)
 // with limit < 2^31).
 //
-// A tile (64 queries) issues exactly its input loads and two masked stores:
-// the status bytes and one 8-B hit record {query, first entry | count << 16}
-// per SOME / OVERFLOW query, at the back of the wave's worklist region.  The
+// A tile (64 queries) issues exactly its input loads and one masked store,
+// the status bytes.  Its hit records, one per SOME / OVERFLOW query, go to the
+// wave's LDS slot behind the pair image (5 B each, OutArgs::lds_hits) while
+// they fit, and from the first tile that does not fit as 8-B records {query,
+// first entry | count << 16} to the back of the wave's worklist region, in a
+// rare wave-uniform branch (always there when lds_hits is 0).  The
 // candidates' bytes are not written in the loop: after its tiles each wave
 // turns its hit records into the result (payload bytes from the LDS pair
 // list): on the device path (fused) the dense hit list and the dense payload,
@@ -1810,7 +1813,7 @@ __device__ __forceinline__ T karg_load(KargPtr p, size_t off) {
 
 template <bool THR, bool MODS>
 __device__ __forceinline__ void scan_end_phase(uint32_t bid, uint32_t nbid, uint32_t w_in, int lane, uint32_t n_hit,
-                                               uint32_t n_staged, uint32_t n_work, uint32_t st_q,
+                                               uint32_t lds_end, uint32_t n_staged, uint32_t n_work, uint32_t st_q,
                                                uint32_t st_payload);
 
 template <bool THR, bool MODS>
@@ -1845,7 +1848,11 @@ __device__ __forceinline__ void explain_scan_wg(const ScanArgs& a, const uint32_
   const uint32_t wave = bid * (kScanWG / 64) + w_in;
   const uint32_t n_waves = nbid * (kScanWG / 64);
   const uint32_t n = (uint32_t)q.n;  // < 2^32 - 64 (host checks)
-  const uint32_t ntiles = (n + 63) >> 6;
+  // a tile exists iff its first query does (batches are capped at 2^29
+  // queries, so tile * 64 cannot wrap): the loop holds the last query's index
+  // and neither n nor a tile count beside it
+  const uint32_t n1 = n - 1;  // (n >= 1: the host launches no empty batch)
+  auto has_tile = [&](uint32_t tl) { return (tl << 6) <= n1; };
   const double limitf = (double)t.limit;
   uint32_t st_q = 0, st_payload = 0;  // per lane: pair-path queries, their payload bytes (+ 2 pad bytes each)
   uint4* wl = out.work + (uint64_t)wave * out.work_region;
@@ -1856,6 +1863,19 @@ __device__ __forceinline__ void explain_scan_wg(const ScanArgs& a, const uint32_
   const __amdgpu_buffer_rsrc_t wl_rsrc = buf_rsrc(wl, wl_bytes);
   const __amdgpu_buffer_rsrc_t st_rsrc = buf_rsrc(out.status, n);
   uint32_t n_hit = 0;  // wave-uniform
+  // The records stay on chip while they fit: record k of the wave lies in its
+  // LDS slot behind the pair image (kHit*: a u32 and a u8 array per wave) for
+  // k < lds_end, and in the worklist region otherwise.  lds_end starts as the
+  // slot's capacity; the first tile whose records do not fit the slot or the
+  // record's fields lowers it to the wave's record count there, so that tile
+  // and every later one of the wave go to the worklist region (wave-uniform,
+  // sticky).  Only this wave reads its records (scan_end_phase).
+  uint8_t* const hit_slot = (uint8_t*)lds_pair_img + n_img16 * 16u + scan_hit_slot(out.lds_hits, w_in);
+  uint32_t lds_end = out.lds_hits;  // wave-uniform
+  uint32_t ord = 0;                 // the tile's ordinal within the wave
+  // (one limit for the MODS variants' budget test: no modification rows = no
+  // bound; they have no SGPR to spare in the loop)
+  const uint32_t w_min_mod = t.any_mod ? (uint32_t)t.w_min_mod : UINT32_MAX;
   // deferred-class windows (deep / exact / no-memo): staged in the wave's own
   // slots during the tiles, copied to the class lists after them with one
   // atomic per class per workgroup -- atomics of every wave on the shared
@@ -1867,14 +1887,14 @@ __device__ __forceinline__ void explain_scan_wg(const ScanArgs& a, const uint32_
   // Loads are unconditional (index clamped to the last query), streamed once
   // (nontemporal).
   auto fetch = [&](uint32_t tl, double& m, double& tt, int64_t& mm) {
-    const uint32_t j = tl < ntiles ? min(tl * 64 + lane, n - 1) : n - 1;
+    const uint32_t j = min(tl * 64 + lane, n1);
     m = __builtin_nontemporal_load(q_at(q.mass, j));
     if (THR) tt = __builtin_nontemporal_load(q_at(q.thr, j));
     if (MODS) mm = __builtin_nontemporal_load(q_at(q.max_mods, j));
   };
   auto step = [&](uint32_t tile, double m_in, double t_in, int64_t mm_cur) {
     const uint32_t i = tile * 64 + lane;
-    const bool live = i < n;
+    const bool live = i <= n1;
     const double m_cur = m_in, t_cur = THR ? t_in : q.tol * m_in;
     double lof, hif;
     quantise_lean_fn(m_cur, t_cur, [] { return SCAN_KARG(scan_karg(), q.prec); }, q.rprec, lof, hif);
@@ -1887,7 +1907,7 @@ __device__ __forceinline__ void explain_scan_wg(const ScanArgs& a, const uint32_
     bool pair, a0ok = true;  // (never: the fast-path theorem, taken in the routing block, its only reader)
     if (MODS) {  // fast-path theorem per lane (budgets_never_bind on u32 values)
       const int A0 = clamp_budget(mm_cur);
-      a0ok = !t.any_mod || A0 >= kInfBudget || (uint64_t)hi < (uint64_t)(A0 + 1) * (uint64_t)t.w_min_mod;
+      a0ok = A0 >= kInfBudget || (uint64_t)hi < (uint64_t)(A0 + 1) * (uint64_t)w_min_mod;  // (hi < 2^31)
       pair = active && a0ok && hi < t.pair_lim;
     } else {
       pair = active && hi < q.pair_hi_lim;
@@ -1903,10 +1923,24 @@ __device__ __forceinline__ void explain_scan_wg(const ScanArgs& a, const uint32_
     // SOME / OVERFLOW status bytes; the hit records (pair path only: cnt == 0 off it)
     const uint64_t hbal = __ballot(cnt != 0);
     const uint32_t hpos = n_hit + mbcnt(hbal);
+    const uint32_t n_hit1 = n_hit + (uint32_t)__builtin_popcountll(hbal);
+    const bool keep = n_hit1 <= lds_end && !__ballot(cnt > kHitMaxCount) && ord <= kHitMaxOrd;  // wave-uniform
+    if (!keep) lds_end = min(lds_end, n_hit);
     __builtin_amdgcn_raw_buffer_store_b8((uint8_t)status, st_rsrc, (live && !work) ? i : kBufSkip, 0, 0);
-    const u32x2 rv = {i, first | (cnt << 16)};
-    __builtin_amdgcn_raw_buffer_store_b64(rv, wl_rsrc, cnt ? wl_bytes - 8u * (hpos + 1u) : kBufSkip, 0, 0);
-    n_hit += (uint32_t)__builtin_popcountll(hbal);
+    if (cnt && keep) {  // consecutive slots: no bank conflicts
+      ((uint32_t*)hit_slot)[hpos] = first | ((uint32_t)lane << kHitFirstBits) | (ord << (kHitFirstBits + kHitLaneBits));
+      *(hit_slot - 1 - hpos) = (uint8_t)cnt;
+    }
+    // the worklist store in a wave-uniform rare branch, like the routing
+    // block's: the common path's vector-memory count per tile stays fixed (the
+    // loads and the status store).  (Kept unconditional with every lane masked
+    // while the wave has not spilled: +0.75 us per step, same-box A/B.)
+    if (!keep && hbal) {
+      const u32x2 rv = {i, first | (cnt << 16)};
+      __builtin_amdgcn_raw_buffer_store_b64(rv, wl_rsrc, cnt ? wl_bytes - 8u * (hpos + 1u) : kBufSkip, 0, 0);
+    }
+    n_hit = n_hit1;
+    ++ord;
     if (__ballot(work)) {  // wave-uniform, rare here: route the window now, so that the deferred class lists
                            // are complete when the scan ends (one tail launch runs every class)
       // (the class's role reads the window's bitset words itself: a window
@@ -1917,23 +1951,22 @@ __device__ __forceinline__ void explain_scan_wg(const ScanArgs& a, const uint32_
       bool never;
       if (MODS) {  // per-query budgets: the fast-path limit of the query's caps
         const int32_t* const qlen = SCAN_KARG(ka, q.qlen);
-        const uint32_t nl = qlen ? SCAN_KARG(ka, q.never_len)[qlen[live ? i : n - 1]] : SCAN_KARG(ka, t.never_lim);
+        const uint32_t nl = qlen ? SCAN_KARG(ka, q.never_len)[qlen[live ? i : n1]] : SCAN_KARG(ka, t.never_lim);
         never = a0ok && hi < nl;
       } else {
         never = hi < SCAN_KARG(ka, q.never_hi_lim);
       }
-      int cls = -1;
-      if (work) {
-        if (never && hi < SCAN_KARG(ka, t.shallow_hi)) {
-          cls = kClassShallow;  // <= 3 items, budgets cannot bind: the SHALLOW role writes the result
-        } else {
-          cls = never ? kClassDeep : (SCAN_KARG(ka, q.with_memo) ? kClassExact : kClassNomemo);
-          SCAN_KARG(ka, out.status)[i] = (int8_t)kStatusPending;
-        }
-      }
+      // (selects and two masked stores, no nested branches: each nesting
+      // level holds an exec mask in an SGPR pair, which the MODS variants do
+      // not have to spare here)
+      // SHALLOW: <= 3 items, budgets cannot bind: its role writes the result
+      const bool shallow = never && hi < SCAN_KARG(ka, t.shallow_hi);
+      const uint32_t deferred = never ? kClassDeep : (SCAN_KARG(ka, q.with_memo) ? kClassExact : kClassNomemo);
+      const uint32_t cls = shallow ? (uint32_t)kClassShallow : deferred;
+      if (work && !shallow) SCAN_KARG(ka, out.status)[i] = (int8_t)kStatusPending;
       uint32_t* const stage = SCAN_KARG(ka, out.stage) + (uint64_t)wave * SCAN_KARG(ka, out.work_region);
-      const uint64_t cb = __ballot(cls >= 0);
-      if (cls >= 0) stage[n_staged + mbcnt(cb)] = i | ((uint32_t)cls << 30);
+      const uint64_t cb = __ballot(work);
+      if (work) stage[n_staged + mbcnt(cb)] = i | (cls << 30);
       n_staged += (uint32_t)__builtin_popcountll(cb);
     }
   };
@@ -1948,6 +1981,9 @@ __device__ __forceinline__ void explain_scan_wg(const ScanArgs& a, const uint32_
   // two dropped stores where a tile's stores would be: the loop entry then has
   // the same VMEM count between the two prefetches as every later round, so
   // the compiler's waits at the loop head are exact on both paths into it
+  // (a tile issues one store on its common path since its hit records go to
+  // LDS: the entry's second one only makes the first tile's wait cover a
+  // dropped store)
   __builtin_amdgcn_raw_buffer_store_b8(0, st_rsrc, kBufSkip, 0, 0);
   __builtin_amdgcn_raw_buffer_store_b8(1, st_rsrc, kBufSkip + 64u, 0, 0);
   fetch(vw + n_waves, mB, tB, mmB);
@@ -1955,22 +1991,26 @@ __device__ __forceinline__ void explain_scan_wg(const ScanArgs& a, const uint32_
   for (int j = 0; j < kImgPieces; ++j)
     if (threadIdx.x + j * kScanWG < n_img16) ((u32x4*)lds_pair_img)[threadIdx.x + j * kScanWG] = img[j];
   __syncthreads();
-  for (uint32_t tile = vw; tile < ntiles; tile += 2 * n_waves) {
+  // (every tile index from the one before it plus n_waves: one stride in an
+  // SGPR, not n_waves and its double)
+  for (uint32_t tile = vw; has_tile(tile);) {
+    const uint32_t t1 = tile + n_waves, t2 = t1 + n_waves;
     step(tile, mA, tA, mmA);
-    fetch(tile + 2 * n_waves, mA, tA, mmA);
-    if (tile + n_waves >= ntiles) break;
-    step(tile + n_waves, mB, tB, mmB);
-    fetch(tile + 3 * n_waves, mB, tB, mmB);
+    fetch(t2, mA, tA, mmA);
+    if (!has_tile(t1)) break;
+    step(t1, mB, tB, mmB);
+    fetch(t2 + n_waves, mB, tB, mmB);
+    tile = t2;
   }
-  scan_end_phase<THR, MODS>(bid, nbid, w_in, lane, n_hit, n_staged, n_work, st_q, st_payload);
+  scan_end_phase<THR, MODS>(bid, nbid, w_in, lane, n_hit, lds_end, n_staged, n_work, st_q, st_payload);
 }
 
 // The scan's end phase: everything a scan wave does after its tiles, from
 // its loop state and the arguments as the kernarg segment holds them.
 template <bool THR, bool MODS>
 __device__ __forceinline__ void scan_end_phase(const uint32_t bid, const uint32_t nbid, const uint32_t w_in,
-                                               const int lane, const uint32_t n_hit, const uint32_t n_staged,
-                                               const uint32_t n_work, const uint32_t st_q,
+                                               const int lane, const uint32_t n_hit, const uint32_t lds_end,
+                                               const uint32_t n_staged, const uint32_t n_work, const uint32_t st_q,
                                                const uint32_t st_payload) {
   extern __shared__ uint32_t lds_pair_img[];
   const KargPtr ka = scan_karg();
@@ -2003,7 +2043,10 @@ __device__ __forceinline__ void scan_end_phase(const uint32_t bid, const uint32_
   __shared__ uint32_t wg_pre[2];
   __shared__ uint32_t wg_cls[kScanWG / 64][kNumClasses];  // per wave: SHALLOW items, staged class windows
   __shared__ uint32_t wg_cls_base[kNumClasses];
-  // this wave's hit records, staged windows and counter adds have landed
+  // this wave's worklist hit records, staged windows and counter adds have
+  // landed.  (Skipped by waves that have none of the three: no difference,
+  // same-box A/B; the wait stays unconditional.)
+  const uint32_t k_lds = min(lds_end, n_hit);  // records [0, k_lds) are in the wave's LDS slot
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   uint32_t n_cls[kNumClasses] = {0u, 0u, 0u, 0u};
   for (uint32_t k0 = 0; k0 < n_staged; k0 += 64) {  // its staged windows per class
@@ -2038,7 +2081,18 @@ __device__ __forceinline__ void scan_end_phase(const uint32_t bid, const uint32_
   // The first kPreChunks x 64 hit records, their payload sizes (LDS) and
   // wave-relative offsets are taken after this workgroup published its totals and before its
   // look-back, so that this work overlaps the wait for the workgroups before this one
-  const uint2* rec = (const uint2*)(wl + out.work_region);  // record k at rec[-1 - k]
+  const uint2* rec = (const uint2*)(wl + out.work_region);  // worklist record k at rec[-1 - k]
+  const uint32_t n_img16 = (uint32_t)(2 * (SCAN_KARG(ka, t.n_pairs) + 2) + SCAN_KARG(ka, t.n_buckets) + 3) >> 2;
+  const uint8_t* const hit_slot = (const uint8_t*)lds_pair_img + n_img16 * 16u + scan_hit_slot(out.lds_hits, w_in);
+  const uint32_t vw = (((w_in >> 1) * nbid + bid) << 1) | (w_in & 1u), n_waves = nbid * (kScanWG / 64);
+  auto hit_rec = [&](uint32_t k) {  // record k {query, first entry | count << 16}: LDS slot or worklist region
+    if (k < k_lds) {
+      const uint32_t w = ((const uint32_t*)hit_slot)[k], c = *(hit_slot - 1 - k);
+      const uint32_t tile = vw + (w >> (kHitFirstBits + kHitLaneBits)) * n_waves;
+      return make_uint2(tile * 64u + ((w >> kHitFirstBits) & 63u), (w & ((1u << kHitFirstBits) - 1u)) | (c << 16));
+    }
+    return *(rec - 1 - k);
+  };
   const uint32_t nh_copy = (out.dbg & 1) ? 0 : n_hit;
   uint2 rr[kPreChunks];
   uint32_t pbv[kPreChunks], inclv[kPreChunks], rel[kPreChunks + 1];
@@ -2046,7 +2100,7 @@ __device__ __forceinline__ void scan_end_phase(const uint32_t bid, const uint32_
 #pragma unroll
   for (int c = 0; c < kPreChunks; ++c) {
     const uint32_t k = c * 64 + lane;
-    rr[c] = k < nh_copy ? *(rec - 1 - k) : make_uint2(0, 0);
+    rr[c] = k < nh_copy ? hit_rec(k) : make_uint2(0, 0);
   }
 #pragma unroll
   for (int c = 0; c < kPreChunks; ++c) {
@@ -2157,7 +2211,7 @@ __device__ __forceinline__ void scan_end_phase(const uint32_t bid, const uint32_
   uint64_t run = pbase + rel[kPreChunks];
   for (uint32_t k0 = kPreChunks * 64; k0 < nh_copy; k0 += 64) {
     const uint32_t k = k0 + lane;
-    const uint2 r = k < n_hit ? *(rec - 1 - k) : make_uint2(0, 0);
+    const uint2 r = k < n_hit ? hit_rec(k) : make_uint2(0, 0);
     const uint32_t cnt = r.y >> 16;
     const uint32_t pb = (k < n_hit && cnt <= q.cap32) ? pair_bytes(pl, r.y & 0xFFFFu, cnt) + 2u : 0u;
     const uint32_t incl = wave_incl_scan32(pb);
@@ -3893,7 +3947,7 @@ size_t scan_dyn_lds(const TableArgs& t) {
 hipError_t launch_explain_scan(const TableArgs& t, const QueryArgs& q, const OutArgs& o, int n_blocks,
                                hipStream_t st) {
   if (q.n <= 0) return hipSuccess;
-  const size_t dyn = scan_dyn_lds(t);
+  const size_t dyn = scan_dyn_lds(t) + scan_hit_lds_bytes(o.lds_hits);
   const ScanArgs a{t, q, o};
   if (!t.pairs_enabled)
     hipLaunchKernelGGL(k_bitset_scan, dim3(n_blocks), dim3(kScanWG), 0, st, t, q, o);
@@ -3911,7 +3965,7 @@ hipError_t launch_step(const TableArgs& t, const QueryArgs& q, const OutArgs& o,
                        int64_t n_peaks, const double* shifts4, double tol, double prec, int8_t* valid_out,
                        hipStream_t st) {
   if (!t.pairs_enabled || q.n <= 0) return hipErrorInvalidValue;
-  const size_t dyn = scan_dyn_lds(t);
+  const size_t dyn = scan_dyn_lds(t) + scan_hit_lds_bytes(o.lds_hits);
   ValidArgs v{t.valid, t.limit, t.full_lo, t.full_hi, t.first_reach, obs, nullptr, n_peaks, tol, prec, 1.0 / prec,
               valid_out};
   PeakShifts sh{};
@@ -3947,6 +4001,49 @@ int explain_scan_blocks_per_cu(size_t dyn) {
   // every variant of the pair scan is held to 8 waves/SIMD by its launch bounds
   return dyn ? occupancy((const void*)k_explain_scan<true, false>, kScanWG, dyn)
              : occupancy((const void*)k_bitset_scan, kScanWG, 0);
+}
+// The pair scan's eight kernels (every THR / MODS variant of both)
+static const void* const kScanKernels[] = {
+    (const void*)k_explain_scan<false, false>, (const void*)k_explain_scan<false, true>,
+    (const void*)k_explain_scan<true, false>,  (const void*)k_explain_scan<true, true>,
+    (const void*)k_step<false, false>,         (const void*)k_step<false, true>,
+    (const void*)k_step<true, false>,          (const void*)k_step<true, true>};
+// Dynamic LDS a scan launch may ask for on the current device: half a CU's
+// LDS when the runtime grants it (launches above the 64 KB default need the
+// attribute; set once per context, which keeps the answer), the default
+// otherwise.
+size_t scan_allow_large_lds() {
+  bool ok = true;
+  for (const void* k : kScanKernels)
+    ok = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kCuLdsBytes / 2)) == hipSuccess && ok;
+  (void)hipGetLastError();
+  return ok ? kCuLdsBytes / 2 : 64 * 1024;
+}
+// Hit records per scan wave that fit in LDS behind an `img`-byte pair image
+// with the occupancy unchanged: the largest K for which two 1024-lane
+// workgroups fit a CU, 2 * (img + region(K) + static __shared__) <= the CU's
+// LDS -- the plain pass runs two scan workgroups per CU, the fused step a
+// scan and an is_valid workgroup, which reserves the same dynamic LDS.  The
+// occupancy queries confirm it; K shrinks until they do (never the occupancy).
+uint32_t scan_lds_hits_max(size_t img, size_t dyn_max) {
+  if (!img) return 0;
+  size_t stat = 0;
+  for (const void* k : kScanKernels) {
+    hipFuncAttributes fa{};
+    if (hipFuncGetAttributes(&fa, k) == hipSuccess) stat = std::max(stat, (size_t)fa.sharedSizeBytes);
+  }
+  (void)hipGetLastError();
+  const size_t room = std::min(kCuLdsBytes / 2, dyn_max + stat);
+  if (img + stat + 16 > room) return 0;
+  uint32_t K = (uint32_t)((room - img - stat - 16) / scan_hit_lds_bytes(4)) * 4u;  // (5 B a record, in fours)
+  const int want = explain_scan_blocks_per_cu(img);
+  auto fits = [&](uint32_t k) {
+    const size_t dyn = img + scan_hit_lds_bytes(k);
+    return explain_scan_blocks_per_cu(dyn) >= want &&
+           occupancy((const void*)k_step<true, false>, kScanWG, dyn) >= std::min(want, 2);
+  };
+  while (K > 0 && !fits(K)) K = K > 16 ? K - 16 : 0;
+  return K;
 }
 int explain_expand_blocks_per_cu() { return occupancy((const void*)k_explain_expand, kWG, 0); }
 hipError_t launch_result_pack(const PackArgs& p, hipStream_t st) {
