@@ -96,6 +96,43 @@ int sst_table_build(sst_ctx* ctx, const int64_t* masses, int n_rows, int64_t max
 int sst_table_upload(sst_ctx* ctx, const int64_t* masses, int n_rows, const void* words, int64_t n_cols,
                      int compression, sst_table** out);
 
+/* Prove on the device that an uploaded table is the table set_up_bit_table
+ * (mass_table.py:207-248) produces for its masses, and give it the state of a
+ * table built here.  An uploaded table is otherwise only known to satisfy
+ * bit0(r, m) == any(r - 1, m), which involves neither the masses nor bit1
+ * (the reference's cache key ignores the alphabet: a .npy written for other
+ * masses with the same row count loads silently, load_dp_table :319-340), so
+ * it has no pair list: its explain passes run the bitset scan, the length
+ * bound has neither fast path nor frontier, and sst_step_rows_device,
+ * sst_explain_pairs_alpha* and the sst_pipe_* / bins / dict / walk stages
+ * refuse it.
+ * Criterion, every word against words of the same table, with pair(r, m) the
+ * 2-bit cell of mass m (bit0 low, bit1 the "left" bit):
+ *   row 0: pair(0, 0) = 3, all other cells 0 (:215-216);
+ *   row r >= 1: bit0(r, m) = [pair(r - 1, m) != 0] (:221-223),
+ *               bit1(r, m) = [m >= w_r and pair(r, m - w_r) != 0] (:230-243);
+ *   last column: word == expected & ((full << 2k) & full) for one k in
+ *   [0, compression] shared by all rows (:246; max_mass is not known here).
+ * By induction over rows, then masses, a table that passes is the built one.
+ * Certifiable are alphabets whose rows r >= 1 all have w_r >= compression
+ * (rows below follow the reference's literal in-place sweep, a zero row leaves
+ * the fixpoint open).  One read-only streaming pass, 16 bytes of output, no
+ * scratch buffer.  Takes the ctx lock and waits for the ctx's queued work.
+ *   built here or certified before: *certified = 1, nothing runs;
+ *   not certifiable: SST_OK, *certified = 0, the table stays as it is;
+ *   violation: SST_E_TABLE, first_bad = {row, column} of the first violating
+ *     word in row-major order (may be NULL; {-1, -1} otherwise), and
+ *     sst_last_error names row, column and the word's mass range.  In the last
+ *     column the violating row is the first at which no k fits all rows so
+ *     far.  The table stays usable exactly as before the call;
+ *   pass: *certified = 1; closure fast paths on, pair list, buckets and census
+ *     built, the scan limits refreshed under the budgets set earlier
+ *     (sst_table_set_budgets), as after sst_table_build.
+ * A result created on this table before certification stays valid and keeps
+ * the bitset scan it was sized for whenever it is reused on this table; new
+ * results take the pair scan. */
+int sst_table_certify(sst_table* t, int* certified, int64_t* first_bad /* [2] row, column; may be NULL */);
+
 /* Row budgets the explain DFS reads from DynamicProgrammingTable.masses:
  * is_mod[r] = NucleotideMass.is_modification, cap[r] =
  * round(seq.max_len * NucleotideMass.modification_rate)
@@ -991,6 +1028,7 @@ int64_t sst_pyset_order(const int32_t* keys, const int64_t* hashes, int64_t n, i
 #define SST_K_PAIRS_ALPHA 17  /* k_pairs_alpha (sst_explain_pairs_alpha*) */
 #define SST_K_REQUERY_MERGE 18 /* k_requery_count + k_scan_u32 + k_requery_copy (sst_requery_merge_device) */
 #define SST_K_HANDOFF 19 /* k_handoff_count + k_scan_u32, k_handoff_emit (sst_handoff_*_device) */
+#define SST_K_TABLE_CERTIFY 20 /* k_table_certify (sst_table_certify) */
 #define SST_K_COUNT 24
 /* When enabled, every kernel launch of this ctx is bracketed by hipEvents
  * recorded on the ctx stream; sst_profile_read synchronises and returns the

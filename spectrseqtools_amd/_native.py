@@ -38,7 +38,7 @@ EXPORTS = (
     "sst_reach_rows_device", "sst_length_bounds_reach_device", "sst_jaccard_device", "sst_skeleton_alpha_device",
     "sst_dict_list_device", "sst_fix_finish_device", "sst_pipe_reserve_rows", "sst_reach_lowest_device",
     "sst_length_bounds_frontier_device", "sst_post_skeleton_device", "sst_ctx_trim", "sst_requery_merge_device",
-    "sst_handoff_count_device", "sst_handoff_emit_device", "sst_table_scan_lds_hits",
+    "sst_handoff_count_device", "sst_handoff_emit_device", "sst_table_scan_lds_hits", "sst_table_certify",
 )
 
 # kernel ids of sst_profile_read
@@ -46,6 +46,7 @@ K_IS_VALID, K_EXPLAIN_SCAN, K_EXPLAIN_DEEP, K_EXPLAIN_NOMEMO, K_EXPLAIN_EXACT, K
 K_RESULT_PACK = 6
 (K_CLASSIFY_ROWS, K_FIX_ROUND, K_VALID_ALPHA, K_BINS_COUNT, K_BINS_EMIT, K_DICT, K_SKEL_WALK, K_REACH_ROWS,
  K_LENGTH_BOUND, K_JACCARD, K_PAIRS_ALPHA, K_REQUERY_MERGE, K_HANDOFF) = range(7, 20)
+K_TABLE_CERTIFY = 20
 K_COUNT = 24  # SST_K_COUNT
 KERNEL_NAMES = {K_IS_VALID: "k_is_valid", K_EXPLAIN_SCAN: "k_explain_scan", K_EXPLAIN_DEEP: "k_explain_deferred",
                 K_EXPLAIN_EXPAND: "k_explain_expand",
@@ -54,7 +55,7 @@ KERNEL_NAMES = {K_IS_VALID: "k_is_valid", K_EXPLAIN_SCAN: "k_explain_scan", K_EX
                 K_BINS_COUNT: "k_bins_count", K_BINS_EMIT: "k_bins_emit", K_DICT: "k_dict_build",
                 K_SKEL_WALK: "k_skel_walk", K_REACH_ROWS: "k_reach_rows", K_LENGTH_BOUND: "k_length_bound",
                 K_JACCARD: "k_jaccard", K_PAIRS_ALPHA: "k_pairs_alpha", K_REQUERY_MERGE: "k_requery_merge",
-                K_HANDOFF: "k_handoff"}
+                K_HANDOFF: "k_handoff", K_TABLE_CERTIFY: "k_table_certify"}
 
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
@@ -203,6 +204,7 @@ def load_library(path=LIB_PATH):
     lib.sst_ctx_synchronize.argtypes = [_P]
     lib.sst_table_build.argtypes = [_P, _P, _I, _I64, _I, _PP]
     lib.sst_table_upload.argtypes = [_P, _P, _I, _P, _I64, _I, _PP]
+    lib.sst_table_certify.argtypes = [_P, ctypes.POINTER(_I), ctypes.POINTER(_I64)]
     lib.sst_table_set_budgets.argtypes = [_P, _P, _P]
     lib.sst_table_shape.argtypes = [_P, ctypes.POINTER(_I), ctypes.POINTER(_I64), ctypes.POINTER(_I)]
     lib.sst_table_download.argtypes = [_P, _P]
@@ -677,6 +679,7 @@ class DeviceTable:
         self.compression = compression
         self.masses = list(masses)
         self._budgets = None
+        self._certified = False
 
     @classmethod
     def build(cls, masses, max_mass, compression, engine=None):
@@ -685,10 +688,50 @@ class DeviceTable:
         h = ctypes.c_void_p()
         engine.check(engine._lib.sst_table_build(engine.handle, _ptr(w), len(w), int(max_mass), int(compression),
                                                  ctypes.byref(h)), "sst_table_build")
-        return cls._wrap(engine, h, w)
+        t = cls._wrap(engine, h, w)
+        t._certified = True
+        return t
 
     @classmethod
-    def upload(cls, masses, words, compression, engine=None):
+    def upload(cls, masses, words, compression, engine=None, certify=False):
+        """Adopt packed words (sst_table_upload).  certify=True also runs
+        certify(): a table that is not set_up_bit_table's for `masses` raises
+        EngineError, one that cannot be certified stays a plain upload."""
+        t = cls._upload(masses, words, compression, engine)
+        if certify:
+            try:
+                t.certify()
+            except Exception:
+                t.close()
+                raise
+        return t
+
+    @property
+    def certified(self):
+        """True for a table built here or one certify() has proven to be the
+        built one (which then has the closure fast paths and the pair list a
+        built table of these masses has)."""
+        return self._certified
+
+    def certify(self):
+        """Prove on the device that the words are the table set_up_bit_table
+        builds for self.masses and unlock what a built table has
+        (sst_table_certify).  True: certified (or built here); False: not
+        certifiable (a row mass below the compression), the table stays as it
+        is.  Raises EngineError on a violation, with the first violating
+        word's (row, column) as its `first_bad`; the table stays usable."""
+        ok, bad = _I(), (_I64 * 2)(-1, -1)
+        rc = self.engine._lib.sst_table_certify(self.handle, ctypes.byref(ok), bad)
+        try:
+            self.engine.check(rc, "sst_table_certify")
+        except EngineError as e:
+            e.first_bad = (int(bad[0]), int(bad[1]))
+            raise
+        self._certified = bool(ok.value)
+        return self._certified
+
+    @classmethod
+    def _upload(cls, masses, words, compression, engine=None):
         engine = engine or get_engine()
         w = np.ascontiguousarray(masses, dtype=np.int64)
         words = np.ascontiguousarray(words, dtype=_DT[compression])

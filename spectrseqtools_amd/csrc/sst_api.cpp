@@ -135,7 +135,8 @@ struct sst_table {
   bool pair_key_set = false;
   int scan_blocks = 0;  // resident workgroups of k_explain_scan (depends on the LDS pair list size)
   uint32_t lds_hits = 0;  // hit records per scan wave kept in LDS by a fused pass (set with scan_blocks)
-  bool closure = false;  // built here from masses >= C: rows are true closures (layered fast paths valid)
+  bool closure = false;  // built here (or certified) from masses >= C: rows are true closures (layered fast paths valid)
+  bool certified = false;  // the words are set_up_bit_table's for `masses`: built here, or sst_table_certify passed
   TableArgs args{};
 };
 
@@ -179,6 +180,10 @@ struct sst_result {
   bool settled = true;     // the current pass has been checked (routed windows run, retries done)
   bool arrays_ready = false;  // count[] / offset[] built from the hit list for the current pass
   bool bitset_scan = false;   // the pass ran k_bitset_scan + k_explain_expand (tables without the pair list)
+  // the table the scan grid was sized for, and whether it had no pair list
+  // then: on that table the result keeps the bitset scan after sst_table_certify
+  const sst_table* sized_for = nullptr;
+  bool sized_bitset = false;
   bool fused_pass = false;    // the pass's scan packed its own queries' result (dense records + payload)
   struct {
     sst_table* t;
@@ -639,6 +644,7 @@ int sst_table_build(sst_ctx* c, const int64_t* masses, int n_rows, int64_t max_m
     delete t;
     return rc;
   }
+  t->certified = true;
   *out = t;
   return SST_OK;
 }
@@ -675,6 +681,68 @@ int sst_table_upload(sst_ctx* c, const int64_t* masses, int n_rows, const void* 
     return rc;
   }
   *out = t;
+  return SST_OK;
+}
+
+int sst_table_certify(sst_table* t, int* certified, int64_t* first_bad) {
+  if (!t || !certified) return SST_E_ARG;
+  sst_ctx* c = t->ctx;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  *certified = t->certified ? 1 : 0;
+  if (first_bad) first_bad[0] = first_bad[1] = -1;
+  if (t->certified) return SST_OK;
+  // literal-sweep rows (0 < w < C) are not closures and a zero-mass row leaves
+  // the fixpoint open: not certifiable, the table stays as it is
+  for (int r = 1; r < t->n_rows; ++r)
+    if (t->masses[r] < t->C) return SST_OK;
+  if (int rc = set_device(c)) return rc;
+  HIP_OK(c, hipStreamSynchronize(c->stream));
+  DevBuf out;
+  if (!out.ensure(16)) return fail(c, SST_E_NOMEM, "device allocation failed (certify)");
+  unsigned long long h[2] = {~0ull, ~0ull};
+  HIP_OK(c, hipMemcpyAsync(out.p, h, 16, hipMemcpyHostToDevice, c->stream));
+  {
+    Prof p(c, SST_K_TABLE_CERTIFY);
+    HIP_OK(c, launch_table_certify(t->C, t->packed.p, (const int*)t->w.p, t->n_rows, t->n_cols,
+                                   (unsigned long long*)out.p, c->stream));
+  }
+  HIP_OK(c, hipMemcpyAsync(h, out.p, 16, hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(c, hipStreamSynchronize(c->stream));
+  if (h[1] == 0) {  // no common last-column mask: the first row that empties the running intersection
+    HIP_OK(c, launch_table_certify_last(t->C, t->packed.p, (const int*)t->w.p, t->n_rows, t->n_cols,
+                                        (unsigned long long*)out.p, c->stream));
+    HIP_OK(c, hipMemcpyAsync(h, out.p, 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+  }
+  out.release();
+  if (h[0] != ~0ull) {
+    const int64_t row = (int64_t)(h[0] >> 32), col = (int64_t)(h[0] & 0xFFFFFFFFull);
+    if (first_bad) first_bad[0] = row, first_bad[1] = col;
+    return fail(c, SST_E_TABLE,
+                "packed table is not the table set_up_bit_table builds for these masses: first violation at row " +
+                    std::to_string(row) + ", column " + std::to_string(col) + " (masses " +
+                    std::to_string(col * t->C) + " to " + std::to_string(col * t->C + t->C - 1) +
+                    (col == t->n_cols - 1 ? "; no last-column mask fits every row)" : ")"));
+  }
+  // the state finish_table(t, true) leaves: closure, pair list / buckets /
+  // census, limits; index and valid are derived from these words already
+  const std::vector<uint8_t> is_mod = t->is_mod;
+  const std::vector<int64_t> cap = t->cap;
+  t->closure = true;
+  int rc = build_pair_list(t, true);
+  if (!rc) rc = sst_table_set_budgets(t, is_mod.data(), cap.data());  // (refresh_limits: never_lim / pair_lim)
+  if (rc) {  // as before the call
+    t->closure = false;
+    t->args.pairs_enabled = 0;
+    t->pair_recs.clear();
+    refresh_limits(t);
+    return rc;
+  }
+  t->pair_key_set = false;
+  t->scan_blocks = 0;  // size_scan again: the scan's dynamic LDS now holds the pair list
+  t->lds_hits = 0;
+  t->certified = true;
+  *certified = 1;
   return SST_OK;
 }
 
@@ -1062,7 +1130,7 @@ int explain_pass(sst_table* t, sst_result* r, const double* d_mass, const double
   ++r->pass_id;
   r->tail_ran = false;
   r->arrays_ready = false;
-  r->bitset_scan = !t->args.pairs_enabled;
+  r->bitset_scan = !t->args.pairs_enabled || (r->sized_for == t && r->sized_bitset);
   if (n == 0 && peaks && peaks->n > 0 && peaks->n_shifts > 0) {
     Prof p(c, SST_K_IS_VALID);
     HIP_OK(c, launch_is_valid_peaks(t->args.valid, t->args.limit, t->args.full_lo, t->args.full_hi,
@@ -1098,6 +1166,7 @@ int explain_pass(sst_table* t, sst_result* r, const double* d_mass, const double
   // values to the deferred roles, which walk the alphabet's rows only
   TableArgs ta = t->args;
   if (d_alpha) ta.pair_lim = 0, ta.shallow_hi = 0;
+  if (r->bitset_scan) ta.pairs_enabled = 0;  // (a result sized before the table was certified)
   QueryArgs q{d_mass, d_thr, d_mods, mods_scalar, n, tol, prec, 1.0 / prec, with_memo, cap_count, kNodeBudget};
   fold_scan_limits(ta, q);
   q.alpha = d_alpha;
@@ -1192,6 +1261,8 @@ int alloc_result(sst_table* t, int64_t n, sst_result** out, bool step = false) {
   r->pass_stream = c->stream;
   r->n = n;
   r->cap_n = n;
+  r->sized_for = t;
+  r->sized_bitset = !t->args.pairs_enabled;
   size_t nn = (size_t)std::max<int64_t>(n, 1);
   // the scan grid: every resident workgroup, or fewer for small batches (16
   // tiles of 64 queries per workgroup at least); worklist: one region per

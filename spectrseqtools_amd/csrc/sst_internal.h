@@ -727,6 +727,13 @@ hipError_t launch_row_literal(int C, const uint64_t* Rprev, int64_t ncols, int s
                               uint64_t* Rout, hipStream_t st);
 hipError_t launch_index(int C, const void* packed, int n_rows, int64_t ncols, int64_t M, ulonglong2* index,
                         uint64_t* valid, int* err, hipStream_t st);
+// certify an uploaded table (sst_certify.hip): out[0] = min row << 32 | column of a violating word, out[1] = the
+// last column's admissible mask set; both ~0 before launch_table_certify.  launch_table_certify_last: the last
+// column's first violating row, when out[1] came back 0
+hipError_t launch_table_certify(int C, const void* packed, const int* w, int n_rows, int64_t n_cols,
+                                unsigned long long* out, hipStream_t st);
+hipError_t launch_table_certify_last(int C, const void* packed, const int* w, int n_rows, int64_t n_cols,
+                                     unsigned long long* out, hipStream_t st);
 hipError_t launch_is_valid(const uint64_t* valid, int64_t limit, int64_t full_lo, int64_t full_hi, int64_t first_reach,
                            const double* mass, const double* thr, int64_t n, double tol, double prec, int8_t* out,
                            hipStream_t st);

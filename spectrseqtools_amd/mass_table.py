@@ -67,7 +67,7 @@ class DynamicProgrammingTable:
     """
 
     def __init__(self, nucleotide_df, compression_rate: int, tolerance: float, precision: float,
-                 seq: SequenceInformation, engine=None, use_cache=False):
+                 seq: SequenceInformation, engine=None, use_cache=False, certify=False):
         self.compression_per_cell = compression_rate
         self.tolerance = tolerance
         self.precision = precision
@@ -86,12 +86,16 @@ class DynamicProgrammingTable:
         # build and write) the .npy cache at set_table_path(); the cache key
         # ignores the alphabet, and a cached table that does not follow the
         # recurrence for self.masses is rejected by the engine's upload check
-        # (the reference would use it silently).
+        # (the reference would use it silently).  That check involves neither
+        # the masses nor the left bits: certify=True also proves the cached
+        # words are set_up_bit_table's for self.masses (certify() below) and
+        # gives the table what a built one has.
         if self._device is None:
             masses = [m.mass for m in self.masses]
             if use_cache:
                 words = load_dp_table(set_table_path(precision, compression_rate), masses, engine=self._engine)
-                self._set_device(_native.DeviceTable.upload(masses, words, compression_rate, engine=self._engine))
+                self._set_device(_native.DeviceTable.upload(masses, words, compression_rate, engine=self._engine,
+                                                            certify=certify))
                 self._table_host = words
             else:
                 self._set_device(_native.DeviceTable.build(masses, max(masses) * MAX_SEQ_LENGTH, compression_rate,
@@ -132,6 +136,19 @@ class DynamicProgrammingTable:
         if c is None:
             raise TypeError(f"unsupported DP table dtype {words.dtype}")
         self._set_device(_native.DeviceTable.upload([m.mass for m in self.masses], words, c, engine=self._engine))
+
+    @property
+    def certified(self):
+        """The device table was built by the engine or certify() has proven it."""
+        return bool(self._device.certified)
+
+    def certify(self):
+        """Prove that an adopted table (use_cache=True, the `table` setter) is
+        the table set_up_bit_table builds for self.masses; a table that passes
+        gets the pair list and the closure fast paths of a built one, which the
+        device pipeline needs (DeviceTable.certify).  False: not certifiable;
+        raises _native.EngineError when the words are another table's."""
+        return self._device.certify()
 
     # -- alphabet adaptation (mass_table.py:86-121) ----------------------------
     def _adapt_individual_modification_rates_by_universal_one(self):
