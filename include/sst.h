@@ -909,6 +909,99 @@ typedef struct sst_handoff_args {
 int sst_handoff_count_device(sst_table* t, const sst_handoff_args* a);
 int sst_handoff_emit_device(sst_table* t, const sst_handoff_args* a);
 
+/* The alignment certificate: which handed-off fragments no window of the
+ * skeleton can explain.  filter_with_lp (prediction.py:229-259) builds and
+ * solves one LinearProgramInstance per fragment only to ask whether the
+ * fragment can sit on a contiguous run of skeleton positions with a mass error
+ * <= tolerance * observed_mass.  A necessary condition is decided here without
+ * a solver; the inputs are the hand-off's dense arrays.
+ * Per spectrum g: L = seq_len[g]; position masks P_0 .. P_{L-1} (two u64 over
+ * table rows, skeleton + 2 pos_off[g]); alphabet mask alpha + 2 g; integer row
+ * masses w_r (the table's, all >= 0); fragments frag_off[g] .. frag_off[g + 1].
+ * Position sets (linear_program.py:109-134): A_i = P_i & alpha if P_i != 0,
+ *   else alpha; row 0 and rows the table does not have are excluded.  If any
+ *   A_i is empty the program has no feasible y: every fragment of the
+ *   spectrum gets SST_ALIGN_INFEASIBLE.
+ * Window of a fragment: target = rint(su / prec) (ties to even), W =
+ *   ceil(tol * obs / prec); an integer sum s fits iff |s - target| <= W
+ *   (W < 0: nothing fits).  su and obs are finite (values beyond +-2^61 after
+ *   the division are clamped there).
+ * Admissible intervals: the contiguous sets of positions with x = 1 under the
+ *   fixings of _set_x (linear_program.py:74-102; later fixings override
+ *   earlier ones) and the contiguity constraints (:206-217), selected by the
+ *   side bits of frag_code (START = bit 2, END = bit 3), mn = frag_min_end,
+ *   mx = frag_max_end:
+ *     START and END ("START_END")  [0, L-1] only (the empty interval if L == 0)
+ *     START only                   [0, r] for r in [min(mn, mx), mx]
+ *     END only                     [l, L-1] for l in [min(mx, mn), mn]
+ *     neither (internal)           every [l, r], 0 <= l <= r < L, and the
+ *                                  empty interval
+ *   The empty interval has sum 0, is written (l, r) = (0xFF, 0xFF), and is
+ *   counted and reported like any other; it fits iff |target| <= W.
+ *   A START-only or END-only fragment with mn or mx outside [0, L-1] is not
+ *   modelled: SST_ALIGN_SKIPPED.  So is every fragment of a spectrum with
+ *   L < 0, L > 253 (sums fit u32 and (l, r) two bytes up to there) or
+ *   pos_off[g + 1] - pos_off[g] != L; an empty A_i takes precedence only
+ *   among modelled spectra.
+ * Achievable sums: S(l, r) = { one w_a per position i in [l, r], a in A_i,
+ *   summed }, LO(l, r) / HI(l, r) the sums of the positions' minima / maxima.
+ * Capacity K = sst_align_capacity() (a build constant >= 1024): [l, r] is
+ *   closed if |S(l, r)| <= K, else open.  |S| never shrinks when an interval
+ *   grows, so this does not depend on the sweep direction.
+ * Outputs per fragment:
+ *   status    SST_ALIGN_NONE: no admissible interval has [target - W,
+ *             target + W] meeting [LO, HI], or every one that does is closed
+ *             and holds no fitting sum; SST_ALIGN_FIT: a closed admissible
+ *             interval holds a fitting sum; SST_ALIGN_OPEN: no closed fit, but
+ *             an open admissible interval's [LO, HI] meets the window
+ *             (undecided); SST_ALIGN_INFEASIBLE, SST_ALIGN_SKIPPED as above.
+ *   alignable 1 for FIT, OPEN, SKIPPED; 0 for NONE, INFEASIBLE.
+ *   n_fit     closed admissible intervals that hold a fitting sum (at most
+ *             253 * 254 / 2 + 1, so the saturating count never saturates).
+ *   first     l << 8 | r of the smallest such (l, r) in (l, r) order (the
+ *             empty interval last, 0xFFFF); 0xFFFE when n_fit == 0.
+ * alignable == 0 is safe: dropping the modification-rate constraints
+ * (linear_program.py:180-196) only enlarges the feasible set, and if no
+ * achievable s has |s - target| <= W then every s has |su / prec - s| >=
+ * W + 1 - 0.5 >= tol * obs / prec + 0.5, so the true error exceeds the
+ * threshold by >= prec / 2, far above the float sums' and a solver's
+ * tolerances; an incumbent is feasible, hence >= the optimum (None becomes
+ * inf, :236), so minimize_error > tol * obs and filter_with_lp removes the
+ * fragment.  This equivalence is proven, not run: no solver is part of this
+ * project's tests.  alignable == 1 promises nothing.
+ * One kernel (k_align_windows, sst_align.hip) queued on the ctx stream; device
+ * pointers; no scratch buffer beyond the outputs.  Fragments of a spectrum in
+ * ascending su order (as the hand-off emits them) run fastest; any order is
+ * answered exactly.  SST_E_ARG: a NULL array with n_spec > 0, n_spec < 0, a
+ * non-positive or non-finite prec, a non-finite tol, a table of more than
+ * SST_MAX_ROWS rows or with a row mass < 0 or >= 2^32 / 253. */
+#define SST_ALIGN_CAPACITY 1024u
+#define SST_ALIGN_NONE 0
+#define SST_ALIGN_FIT 1
+#define SST_ALIGN_OPEN 2
+#define SST_ALIGN_INFEASIBLE 3
+#define SST_ALIGN_SKIPPED 4
+typedef struct sst_align_args {
+  int64_t n_spec;
+  const int32_t* seq_len;       /* [n_spec] */
+  const int64_t* pos_off;       /* [n_spec + 1] */
+  const uint64_t* skeleton;     /* [2 pos_off[n_spec]] */
+  const uint64_t* alpha;        /* [2 n_spec] */
+  const int64_t* frag_off;      /* [n_spec + 1] */
+  const uint8_t* frag_code;     /* [frag_off[n_spec]] each, as sst_handoff_emit_device's code */
+  const double* frag_su;
+  const double* frag_obs;
+  const int32_t* frag_min_end;
+  const int32_t* frag_max_end;
+  double tol, prec;
+  uint8_t* status;              /* outputs, [frag_off[n_spec]] each */
+  uint8_t* alignable;
+  uint32_t* n_fit;
+  uint16_t* first;
+} sst_align_args;
+uint32_t sst_align_capacity(void);
+int sst_align_windows_device(sst_table* t, const sst_align_args* a);
+
 /* compute_sequence_length_bound (mass_table.py:343-487) after the skeleton's
  * alphabet reduction (skeleton_building.py:315-336), both directions, for
  * queries on per-spectrum reduced alphabets, exact without a table rebuild:
@@ -1029,6 +1122,7 @@ int64_t sst_pyset_order(const int32_t* keys, const int64_t* hashes, int64_t n, i
 #define SST_K_REQUERY_MERGE 18 /* k_requery_count + k_scan_u32 + k_requery_copy (sst_requery_merge_device) */
 #define SST_K_HANDOFF 19 /* k_handoff_count + k_scan_u32, k_handoff_emit (sst_handoff_*_device) */
 #define SST_K_TABLE_CERTIFY 20 /* k_table_certify (sst_table_certify) */
+#define SST_K_ALIGN 21 /* k_align_windows (sst_align_windows_device) */
 #define SST_K_COUNT 24
 /* When enabled, every kernel launch of this ctx is bracketed by hipEvents
  * recorded on the ctx stream; sst_profile_read synchronises and returns the

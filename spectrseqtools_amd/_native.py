@@ -39,6 +39,7 @@ EXPORTS = (
     "sst_dict_list_device", "sst_fix_finish_device", "sst_pipe_reserve_rows", "sst_reach_lowest_device",
     "sst_length_bounds_frontier_device", "sst_post_skeleton_device", "sst_ctx_trim", "sst_requery_merge_device",
     "sst_handoff_count_device", "sst_handoff_emit_device", "sst_table_scan_lds_hits", "sst_table_certify",
+    "sst_align_capacity", "sst_align_windows_device",
 )
 
 # kernel ids of sst_profile_read
@@ -47,6 +48,7 @@ K_RESULT_PACK = 6
 (K_CLASSIFY_ROWS, K_FIX_ROUND, K_VALID_ALPHA, K_BINS_COUNT, K_BINS_EMIT, K_DICT, K_SKEL_WALK, K_REACH_ROWS,
  K_LENGTH_BOUND, K_JACCARD, K_PAIRS_ALPHA, K_REQUERY_MERGE, K_HANDOFF) = range(7, 20)
 K_TABLE_CERTIFY = 20
+K_ALIGN = 21
 K_COUNT = 24  # SST_K_COUNT
 KERNEL_NAMES = {K_IS_VALID: "k_is_valid", K_EXPLAIN_SCAN: "k_explain_scan", K_EXPLAIN_DEEP: "k_explain_deferred",
                 K_EXPLAIN_EXPAND: "k_explain_expand",
@@ -55,7 +57,7 @@ KERNEL_NAMES = {K_IS_VALID: "k_is_valid", K_EXPLAIN_SCAN: "k_explain_scan", K_EX
                 K_BINS_COUNT: "k_bins_count", K_BINS_EMIT: "k_bins_emit", K_DICT: "k_dict_build",
                 K_SKEL_WALK: "k_skel_walk", K_REACH_ROWS: "k_reach_rows", K_LENGTH_BOUND: "k_length_bound",
                 K_JACCARD: "k_jaccard", K_PAIRS_ALPHA: "k_pairs_alpha", K_REQUERY_MERGE: "k_requery_merge",
-                K_HANDOFF: "k_handoff", K_TABLE_CERTIFY: "k_table_certify"}
+                K_HANDOFF: "k_handoff", K_TABLE_CERTIFY: "k_table_certify", K_ALIGN: "k_align_windows"}
 
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
@@ -104,6 +106,19 @@ class HandoffArgs(ctypes.Structure):
                                         "active", "seq_len", "comb_off", "comb", "n_frag", "n_pos", "frag_off",
                                         "pos_off", "index", "code", "su", "obs", "out_min_end", "out_max_end",
                                         "skeleton")]
+
+
+class AlignArgs(ctypes.Structure):
+    """sst_align_args (include/sst.h): the alignment certificate over the hand-off's dense arrays."""
+    _fields_ = [("n_spec", ctypes.c_int64)] + \
+        [(n, ctypes.c_void_p) for n in ("seq_len", "pos_off", "skeleton", "alpha", "frag_off", "frag_code", "frag_su",
+                                        "frag_obs", "frag_min_end", "frag_max_end")] + \
+        [("tol", ctypes.c_double), ("prec", ctypes.c_double)] + \
+        [(n, ctypes.c_void_p) for n in ("status", "alignable", "n_fit", "first")]
+
+
+# sst_align_windows_device's status per fragment (SST_ALIGN_*)
+ALIGN_NONE, ALIGN_FIT, ALIGN_OPEN, ALIGN_INFEASIBLE, ALIGN_SKIPPED = range(5)
 
 
 class RequeryMergeArgs(ctypes.Structure):
@@ -322,6 +337,10 @@ def load_library(path=LIB_PATH):
     lib.sst_handoff_count_device.restype = _I
     lib.sst_handoff_emit_device.argtypes = [_P, ctypes.POINTER(HandoffArgs)]
     lib.sst_handoff_emit_device.restype = _I
+    lib.sst_align_capacity.argtypes = []
+    lib.sst_align_capacity.restype = ctypes.c_uint32
+    lib.sst_align_windows_device.argtypes = [_P, ctypes.POINTER(AlignArgs)]
+    lib.sst_align_windows_device.restype = _I
     lib.sst_jaccard_device.argtypes = [_P, ctypes.POINTER(JaccardArgs)]
     lib.sst_jaccard_device.restype = _I
     lib.sst_skeleton_alpha_device.argtypes = [_P, _I64, _P, _P, _P, _P, _P]

@@ -1,0 +1,248 @@
+"""The alignment certificate: which fragments of a BatchOutcome no window of
+the skeleton can explain (include/sst.h, sst_align_windows_device; DESIGN
+"Alignment certificate").
+
+filter_with_lp (prediction.py:229-259) solves one LinearProgramInstance per
+surviving fragment to learn whether it can sit on a contiguous run of
+skeleton positions within tolerance * observed_mass.  A fragment with
+alignable == 0 here is removed by every outcome of that solve, so the solve
+can be skipped; alignable == 1 promises nothing.
+
+align_host is the definition in plain numpy / Python (the mirror for spectra
+run_batch routed to the host, and the model the tests hold the kernel to),
+align_device the kernel (csrc/sst_align.hip) over a whole outcome.
+"""
+import ctypes
+import math
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _native
+from ._native import ALIGN_FIT, ALIGN_INFEASIBLE, ALIGN_NONE, ALIGN_OPEN, ALIGN_SKIPPED
+
+ALIGN_CAPACITY = 1024   # sst_align_capacity(): sums a closed interval may have
+ALIGN_MAX_LEN = 253     # longer skeletons are not modelled (SKIPPED)
+EMPTY_INTERVAL = 0xFFFF  # `first` of the empty interval, (l, r) = (0xFF, 0xFF)
+NO_INTERVAL = 0xFFFE     # `first` when n_fit == 0
+STATUS_NAMES = {ALIGN_NONE: "NONE", ALIGN_FIT: "FIT", ALIGN_OPEN: "OPEN", ALIGN_INFEASIBLE: "INFEASIBLE",
+                ALIGN_SKIPPED: "SKIPPED"}
+_CLAMP = 1 << 61
+
+
+@dataclass
+class AlignOutcome:
+    """The certificate per fragment, parallel to BatchOutcome's fragment
+    arrays (fragment k of spectrum g at frag_off[g] + k), as host arrays."""
+    frag_off: np.ndarray   # [S + 1] i64, the BatchOutcome's
+    status: np.ndarray     # u8 ALIGN_NONE / FIT / OPEN / INFEASIBLE / SKIPPED
+    alignable: np.ndarray  # u8: 0 -> filter_with_lp removes the fragment
+    n_fit: np.ndarray      # u32 closed admissible intervals holding a fitting sum
+    first: np.ndarray      # u16 l << 8 | r of the first of them, NO_INTERVAL if none
+
+    FRAGMENT_FIELDS = ("status", "alignable", "n_fit", "first")
+    _DTYPES = {"frag_off": np.int64, "status": np.uint8, "alignable": np.uint8, "n_fit": np.uint32,
+               "first": np.uint16}
+
+    def __post_init__(self):
+        for k, dt in self._DTYPES.items():
+            setattr(self, k, np.ascontiguousarray(getattr(self, k), dtype=dt))
+        if len(self.frag_off) < 1 or any(len(getattr(self, k)) != int(self.frag_off[-1]) for k in self.FRAGMENT_FIELDS):
+            raise ValueError("AlignOutcome: arrays do not match frag_off")
+
+    def __len__(self):
+        return len(self.frag_off) - 1
+
+    def equals(self, other):
+        return all(np.array_equal(getattr(self, k), getattr(other, k)) for k in self._DTYPES)
+
+    def shares(self):
+        """Share of each status over all fragments, by name."""
+        n = max(1, len(self.status))
+        return {name: float(np.count_nonzero(self.status == st)) / n for st, name in STATUS_NAMES.items()}
+
+    def take(self, idx):
+        """The certificate of spectra idx, in that order (as BatchOutcome.take)."""
+        from .pipeline_device import _segments
+
+        src, off = _segments(self.frag_off, np.asarray(idx, dtype=np.int64))
+        return AlignOutcome(frag_off=off, **{k: getattr(self, k)[src] for k in self.FRAGMENT_FIELDS})
+
+    @classmethod
+    def concat(cls, outcomes):
+        """Several certificates' spectra one after the other (as BatchOutcome.concat)."""
+        outcomes = list(outcomes)
+        if not outcomes:
+            raise ValueError("AlignOutcome.concat: nothing to concatenate")
+        base = np.concatenate([[0], np.cumsum([int(o.frag_off[-1]) for o in outcomes])]).astype(np.int64)
+        off = np.concatenate([o.frag_off[:-1] + b for o, b in zip(outcomes, base)] + [base[-1:]])
+        return cls(frag_off=off, **{k: np.concatenate([getattr(o, k) for o in outcomes]) for k in cls.FRAGMENT_FIELDS})
+
+
+def _clamp(x):
+    return max(-_CLAMP, min(_CLAMP, x))
+
+
+def quantise(su, obs, tolerance, precision):
+    """(target, W) of a fragment: round(su / precision) (ties to even) and
+    ceil(tolerance * obs / precision); a negative W is -1 (nothing fits)."""
+    t = _clamp(round(su / precision)) if math.isfinite(su / precision) else (_CLAMP if su > 0 else -_CLAMP)
+    q = tolerance * obs / precision
+    w = _clamp(math.ceil(q)) if math.isfinite(q) else (_CLAMP if q > 0 else -_CLAMP)
+    return t, (w if w >= 0 else -1)
+
+
+def _rows_of(m0, m1, n_rows):
+    return [r for r in range(1, n_rows) if ((m0 >> r) & 1 if r < 64 else (m1 >> (r - 64)) & 1)]
+
+
+def position_sets(skeleton, alpha, n_rows):
+    """A_i per position as row lists: P_i & alpha where P_i != 0, else alpha; row 0 excluded."""
+    a0, a1 = int(alpha[0]), int(alpha[1])
+    out = []
+    for p in skeleton:
+        p0, p1 = int(p[0]), int(p[1])
+        out.append(_rows_of(p0 & a0, p1 & a1, n_rows) if (p0 | p1) else _rows_of(a0, a1, n_rows))
+    return out
+
+
+def _align_spectrum(L, sets, row_mass, code, su, obs, mn, mx, tolerance, precision, capacity):
+    n = len(code)
+    status = np.zeros(n, np.uint8)
+    n_fit = np.zeros(n, np.int64)
+    first = np.full(n, 1 << 20, np.int64)
+    opened = np.zeros(n, bool)
+    cls = (code.astype(np.int64) >> 2) & 3  # 0 internal, 1 START, 2 END, 3 START_END
+    skipped = ((cls == 1) | (cls == 2)) & ((mn < 0) | (mn >= L) | (mx < 0) | (mx >= L))
+    tw = [quantise(float(s), float(o), tolerance, precision) for s, o in zip(su, obs)]
+    t = np.array([x[0] for x in tw], dtype=np.int64).reshape(n)
+    w = np.array([x[1] for x in tw], dtype=np.int64).reshape(n)
+    live = ~skipped & (w >= 0)
+    flo, fhi = t - w, t + w
+    lo_end = np.minimum(mn, mx)
+    masses = [np.array(sorted({int(row_mass[r]) for r in rows}), dtype=np.int64) for rows in sets]
+
+    def match(ok, l, r, LO, HI, sums):
+        """Fragments `ok` against interval (l, r): sums None for an open one."""
+        cand = np.flatnonzero(ok & live & (fhi >= LO) & (flo <= HI))
+        if not len(cand):
+            return
+        if sums is None:
+            opened[cand] = True
+            return
+        at = np.searchsorted(sums, flo[cand], side="left")
+        fit = cand[(at < len(sums)) & (sums[np.minimum(at, len(sums) - 1)] <= fhi[cand])]
+        n_fit[fit] += 1
+        first[fit] = np.minimum(first[fit], l << 8 | r)
+
+    def sweep(start, step, ok_of):
+        sums, LO, HI = np.zeros(1, np.int64), 0, 0
+        last = int(fhi[live].max()) if live.any() else -1
+        p = start
+        while 0 <= p < L:
+            m = masses[p]
+            LO, HI = LO + int(m[0]), HI + int(m[-1])
+            if LO > last:  # masses are >= 0: LO never falls
+                break
+            if sums is not None:
+                sums = np.unique(np.add.outer(sums, m)) if len(m) > 1 else sums + m[0]
+                if len(sums) > capacity:
+                    sums = None
+            l, r = (start, p) if step > 0 else (p, start)
+            match(ok_of(l, r), l, r, LO, HI, sums)
+            p += step
+
+    internal = cls == 0
+    if internal.any() or (L == 0 and (cls == 3).any()):
+        match(internal | ((cls == 3) & (L == 0)), 0xFF, 0xFF, 0, 0, np.zeros(1, np.int64))
+    for l in range(L if internal.any() else min(L, 1)):
+        if l == 0:
+            sweep(0, 1, lambda l, r: internal | ((cls == 1) & (r >= lo_end) & (r <= mx)) | ((cls == 3) & (r == L - 1)))
+        else:
+            sweep(l, 1, lambda l, r: internal)
+    if (cls == 2).any():
+        sweep(L - 1, -1, lambda l, r: (cls == 2) & (l >= lo_end) & (l <= mn))
+
+    status[:] = np.where(skipped, ALIGN_SKIPPED, np.where(n_fit > 0, ALIGN_FIT, np.where(opened, ALIGN_OPEN, ALIGN_NONE)))
+    return status, n_fit, np.where(n_fit > 0, first, NO_INTERVAL)
+
+
+def align_host(outcome, tolerance, precision, capacity=ALIGN_CAPACITY):
+    """The certificate of every fragment of `outcome` (a BatchOutcome), by the
+    definition: per left end the achievable sums of the growing interval as a
+    sorted array, open once they number more than `capacity`."""
+    S, nf = len(outcome), int(outcome.frag_off[-1])
+    status = np.zeros(nf, np.uint8)
+    n_fit = np.zeros(nf, np.uint32)
+    first = np.full(nf, NO_INTERVAL, np.uint16)
+    n_rows = len(outcome.row_mass)
+    if n_rows and (int(outcome.row_mass.min()) < 0 or int(outcome.row_mass.max()) >= (1 << 32) // ALIGN_MAX_LEN):
+        raise ValueError("align_host: a row mass outside [0, 2^32 / 253)")
+    for g in range(S):
+        f = slice(int(outcome.frag_off[g]), int(outcome.frag_off[g + 1]))
+        if f.start == f.stop:
+            continue
+        L = int(outcome.seq_len[g])
+        p = slice(int(outcome.pos_off[g]), int(outcome.pos_off[g + 1]))
+        if L < 0 or L > ALIGN_MAX_LEN or p.stop - p.start != L:
+            status[f] = ALIGN_SKIPPED
+            continue
+        sets = position_sets(outcome.skeleton[p], outcome.alpha[g], n_rows)
+        if any(not rows for rows in sets):
+            status[f] = ALIGN_INFEASIBLE
+            continue
+        st, nn, ff = _align_spectrum(L, sets, outcome.row_mass, outcome.frag_code[f], outcome.frag_su[f],
+                                     outcome.frag_obs[f], outcome.frag_min_end[f].astype(np.int64),
+                                     outcome.frag_max_end[f].astype(np.int64), tolerance, precision, int(capacity))
+        status[f], n_fit[f], first[f] = st, nn, ff
+    alignable = ((status != ALIGN_NONE) & (status != ALIGN_INFEASIBLE)).astype(np.uint8)
+    return AlignOutcome(frag_off=outcome.frag_off.copy(), status=status, alignable=alignable, n_fit=n_fit, first=first)
+
+
+def align_device(dp_table, outcome):
+    """The certificate of every fragment of `outcome` on dp_table's device
+    (sst_align_windows_device, capacity sst_align_capacity()): one upload per
+    input array, one launch, one download per output array.  `outcome` must be
+    on dp_table's rows."""
+    from .pipeline_device import _one_stream
+
+    masses = [int(m.mass) for m in dp_table.masses]
+    if masses != [int(x) for x in outcome.row_mass]:
+        raise ValueError("align_device: the outcome is not on this table's rows")
+    return _one_stream(_align_device)(dp_table, outcome)
+
+
+def _align_device(dp_table, o):
+    import torch
+
+    dt = dp_table.device_table
+    eng = dt.engine
+    dev = torch.device("cuda", eng.device)
+    S, nf = len(o), int(o.frag_off[-1])
+    if nf == 0:
+        z = np.zeros(0)
+        return AlignOutcome(frag_off=o.frag_off.copy(), status=z, alignable=z, n_fit=z, first=z)
+
+    def up(x, dtype, n=1):  # (never an empty allocation: the entry point refuses NULL)
+        x = np.ascontiguousarray(x, dtype=dtype).reshape(-1)
+        return torch.as_tensor(x if len(x) else np.zeros(n, dtype), device=dev)
+
+    keep = [up(o.seq_len, np.int32), up(o.pos_off, np.int64), up(o.skeleton.view(np.int64), np.int64, 2),
+            up(o.alpha.view(np.int64), np.int64, 2), up(o.frag_off, np.int64), up(o.frag_code, np.uint8),
+            up(o.frag_su, np.float64), up(o.frag_obs, np.float64), up(o.frag_min_end, np.int32),
+            up(o.frag_max_end, np.int32)]
+    status = torch.empty(nf, dtype=torch.uint8, device=dev)
+    alignable = torch.empty(nf, dtype=torch.uint8, device=dev)
+    n_fit = torch.empty(nf, dtype=torch.int32, device=dev)
+    first = torch.empty(nf, dtype=torch.int16, device=dev)
+    a = _native.AlignArgs()
+    a.n_spec = S
+    (a.seq_len, a.pos_off, a.skeleton, a.alpha, a.frag_off, a.frag_code, a.frag_su, a.frag_obs, a.frag_min_end,
+     a.frag_max_end) = (x.data_ptr() for x in keep)
+    a.tol, a.prec = float(dp_table.tolerance), float(dp_table.precision)
+    a.status, a.alignable, a.n_fit, a.first = (x.data_ptr() for x in (status, alignable, n_fit, first))
+    torch.cuda.synchronize(dev)
+    eng.check(eng._lib.sst_align_windows_device(dt.handle, ctypes.byref(a)), "sst_align_windows_device")
+    eng.synchronize()
+    return AlignOutcome(frag_off=o.frag_off.copy(), status=status.cpu().numpy(), alignable=alignable.cpu().numpy(),
+                        n_fit=n_fit.cpu().numpy().view(np.uint32), first=first.cpu().numpy().view(np.uint16))

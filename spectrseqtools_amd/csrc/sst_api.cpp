@@ -3747,6 +3747,26 @@ extern "C" int sst_handoff_emit_device(sst_table* t, const sst_handoff_args* a) 
   return SST_OK;
 }
 
+extern "C" uint32_t sst_align_capacity(void) { return SST_ALIGN_CAPACITY; }
+
+extern "C" int sst_align_windows_device(sst_table* t, const sst_align_args* a) {
+  if (!t || !a || a->n_spec < 0 || a->n_spec > INT32_MAX) return SST_E_ARG;
+  if (!std::isfinite(a->tol) || !std::isfinite(a->prec) || !(a->prec > 0)) return SST_E_ARG;
+  if (a->n_spec == 0) return SST_OK;
+  if (!a->seq_len || !a->pos_off || !a->skeleton || !a->alpha || !a->frag_off || !a->frag_code || !a->frag_su ||
+      !a->frag_obs || !a->frag_min_end || !a->frag_max_end || !a->status || !a->alignable || !a->n_fit || !a->first)
+    return SST_E_ARG;
+  if (t->n_rows > SST_MAX_ROWS) return SST_E_ARG;
+  for (int r = 0; r < t->n_rows; ++r)  // sums of 253 positions stay below 2^32
+    if (t->masses[r] < 0 || t->masses[r] >= (int64_t)(0x100000000ull / 253)) return SST_E_ARG;
+  sst_ctx* c = t->ctx;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  if (int rc = set_device(c)) return rc;
+  Prof p(c, SST_K_ALIGN);
+  HIP_OK(c, sst::launch_align_windows(*a, t->args.w, t->n_rows, 2 * c->n_cu, c->stream));
+  return SST_OK;
+}
+
 extern "C" int sst_skeleton_alpha_device(sst_table* t, int64_t n_spec, const int32_t* d_max_len,
                                          const uint64_t* d_skel_off, const uint64_t* d_skel, const uint64_t* d_alpha,
                                          uint64_t* d_out) {

@@ -1732,7 +1732,7 @@ def mirror_outcome(dp_table, obs, su_mass, seq_mass, max_len, breakage_dict, int
 
 def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=None, intensity=None,
               intensity_cutoff=0.5e6, mass_cutoff=50000, limits=DeviceLimits(), fallback="mirror", name_hash=None,
-              trim=True, explanation_masses=None, record=None):
+              trim=True, explanation_masses=None, record=None, align=False):
     """These spectra -> what Predictor.predict holds when it reaches its MILP
     stages (prediction.py:63-103), as a BatchOutcome: the six device stages
     (classify_device, fixpoint_device, bins_device, skeleton_device,
@@ -1763,7 +1763,13 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
 
     record: a dict that receives diagnostics (walk_status [2 S], lb_status,
     replay_nodes, jaccard_status of the spectra the device ran, device_index
-    their positions in the batch)."""
+    their positions in the batch).
+
+    align=True: also the alignment certificate of every fragment (alignment.py:
+    which fragments no window of the skeleton can explain, so filter_with_lp
+    need not solve for them); returns (BatchOutcome, AlignOutcome).  Spectra
+    the device ran take align_device, mirror-routed ones align_host at the
+    device's capacity; the BatchOutcome is the default call's."""
     from .masses import EXPLANATION_MASSES, TOLERANCE
     from .pipeline import max_len_of
 
@@ -1838,8 +1844,12 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
                                frag_max_end=h["max_end"], breakage_names=names, row_names=dev_out.row_names,
                                row_mass=dev_out.row_mass)
     m_idx = np.flatnonzero(reason)
+    if align:
+        from . import alignment
+
+        dev_al = alignment.align_device(dp_table, dev_out)
     if not len(m_idx):
-        return dev_out
+        return (dev_out, dev_al) if align else dev_out
     mirrored = [mirror_outcome(dp_table, obs[offsets[g]:offsets[g + 1]], su_seq[g], seq_mass[g], max_len[g],
                                breakage_dict, None if inten is None else inten[offsets[g]:offsets[g + 1]],
                                intensity_cutoff, mass_cutoff, em, int(reason[g])) for g in m_idx.tolist()]
@@ -1847,4 +1857,9 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
     where = np.empty(S, np.int64)  # spectrum g's place in `both`: its device slot, or its mirror run
     where[d_idx] = np.arange(len(d_idx))
     where[m_idx] = len(d_idx) + np.arange(len(m_idx))
+    if align:
+        cap = int(dp_table.device_table.engine._lib.sst_align_capacity())
+        al = alignment.AlignOutcome.concat([dev_al] + [alignment.align_host(o, dp_table.tolerance, dp_table.precision, cap)
+                                                       for o in mirrored])
+        return both.take(where), al.take(where)
     return both.take(where)

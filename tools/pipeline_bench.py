@@ -50,6 +50,7 @@ GPU-busy share of its wall time.
 
 Usage: python tools/pipeline_bench.py [--spectra 100000] [--seed 7] [--host-driven]
        [--backend nccl|gloo] [--dump-outcomes DIR] [--as-rank R] [--handoff [--handoff-repeats 3]]
+       [--align]
 """
 import argparse
 import json
@@ -271,6 +272,38 @@ def handoff_timings(pd, dp, rows, ln, post, repeats):
                                      "downloaded whole, compacted with numpy"}}
 
 
+def align_stage(pd, dp, rows, ln, post, kernels):
+    """--align: the alignment certificate (alignment.align_device) over the
+    hand-off of the spectra the stages ran -- wall seconds from the host
+    arrays in to the host arrays out (uploads, k_align_windows, downloads), the
+    kernel's event time, and the share of each status over all fragments.
+    The hand-off itself is not part of the time."""
+    from spectrseqtools_amd import alignment
+
+    S = len(ln.seq_len)
+    act = np.asarray(post.active[:S]) != 0
+    h = pd.handoff_device(dp, rows, ln, post, active=act)
+    empty = pd._empty_outcome(dp, rows.names, 0)
+    out = pd.BatchOutcome(default=~act, route=np.zeros(S, np.uint8), reason=np.zeros(S, np.uint8),
+                          alpha=np.where(act[:, None], post.alpha[:S], np.uint64(0)),
+                          seq_len=np.where(act, ln.seq_len[:S], 0), pos_off=h["pos_off"], skeleton=h["skeleton"],
+                          frag_off=h["frag_off"], frag_index=h["index"], frag_code=h["code"], frag_su=h["su"],
+                          frag_obs=h["obs"], frag_min_end=h["min_end"], frag_max_end=h["max_end"],
+                          breakage_names=rows.names, row_names=empty.row_names, row_mass=empty.row_mass)
+    kernels()  # (the hand-off's launches are not this stage's)
+    t0 = time.perf_counter()
+    al = alignment.align_device(dp, out)
+    s = time.perf_counter() - t0
+    n = np.diff(out.frag_off)
+    internal = (out.frag_code >> 2) & 3 == 0
+    return {"s": s, "spectra": int(act.sum()), "fragments": int(out.frag_off[-1]), "positions": int(out.pos_off[-1]),
+            "fragments_per_spectrum_max": int(n.max()) if S else 0, "seq_len_max": int(out.seq_len.max()) if S else 0,
+            "internal_fragments": int(internal.sum()), "capacity": alignment.ALIGN_CAPACITY,
+            "status_shares": al.shares(), "not_alignable_share": float(1.0 - al.alignable.mean()) if len(al.status) else 0.0,
+            "not_alignable_share_internal": float(1.0 - al.alignable[internal].mean()) if internal.any() else 0.0,
+            "path": "device (sst_align_windows_device), host arrays in and out", "kernels": kernels()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--spectra", type=int, default=100000, help="spectra per GPU")
@@ -304,6 +337,9 @@ def main():
                          "\"handoff\", outside the stages' total")
     ap.add_argument("--handoff-repeats", type=int, default=3, help="--handoff: timed repeats of each way (after one "
                                                                    "untimed run)")
+    ap.add_argument("--align", action="store_true",
+                    help="after the stages, also run the alignment certificate (alignment.align_device) over the "
+                         "hand-off: a stage \"align\" with its seconds and the share of each status over all fragments")
     ap.add_argument("--as-rank", type=int, default=None,
                     help="single process: generate the spectra rank R of a multi-rank run would get")
     args = ap.parse_args()
@@ -398,7 +434,9 @@ def main():
         # (trim=False: a serving process keeps the frontier's workspace across
         # batches; the timed stage reuses the warm-up's, as round 5 did)
         lw = pd.length_device(dp, kw, bw.alpha_dev, su_seq[:S0], batch.seq_mass[:S0], trim=False)
-        pd.post_skeleton_device(dp, rw, kw, lw)
+        pw = pd.post_skeleton_device(dp, rw, kw, lw)
+        if args.align:
+            align_stage(pd, dp, rw, lw, pw, lambda: None)
         # the reach buffer at length_device's batch budget, as a serving
         # process holds it: the timed stage allocates nothing (its hipMalloc /
         # hipFree of tens of GB took 0.1-3 s from run to run)
@@ -564,6 +602,12 @@ def main():
         stages["gather"] = {"s": tmax(time.perf_counter() - t0), "bytes_per_rank": sizes, "kernels": kernels(),
                             "path": "pack_outcomes + one agreed-size gather to rank 0"
                                     + (f" ({'RCCL' if args.backend == 'nccl' else 'gloo'})" if dist else " (local)")}
+    if rows is not None and args.align:
+        barrier()
+        stages["align"] = align_stage(pd, dp, rows, ln, post, kernels)
+        stages["align"]["s"] = tmax(stages["align"]["s"])
+        busy(stages["align"])
+        progress("align")
     handoff = None
     if rows is not None and args.handoff:
         engine.profile(False)  # (the hand-off is timed by the wall clock alone, outside the stages)
