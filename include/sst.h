@@ -1002,6 +1002,41 @@ typedef struct sst_align_args {
 uint32_t sst_align_capacity(void);
 int sst_align_windows_device(sst_table* t, const sst_align_args* a);
 
+/* The two-list split of the certificate's open intervals (an exact
+ * meet-in-the-middle).  Everything of sst_align_windows_device's definition
+ * stays; for an open interval [l, r]:
+ *   [l, r] is split-closed iff there is an m in [l, r - 1] with S(l, m) and
+ *   S(m + 1, r) both closed.  |S| never shrinks when an interval grows, so
+ *   this holds iff it holds for the greedy split from the left (m* the largest
+ *   m with S(l, m) closed) and iff it holds for the greedy split from the
+ *   right: it does not depend on the sweep direction.
+ *   A split-closed interval holds a fitting sum iff some a in S(l, m) and b in
+ *   S(m + 1, r) have |a + b - target| <= W (exact for any valid m, since
+ *   S(l, r) = S(l, m) + S(m + 1, r)).
+ *   An interval that is neither closed nor split-closed is undecided.
+ * Precondition: a's four output arrays hold the result of
+ * sst_align_windows_device for the same a.  Only fragments whose status there
+ * is SST_ALIGN_OPEN are recomputed:
+ *   status    SST_ALIGN_FIT if a split-closed admissible interval holds a
+ *             fitting sum; else SST_ALIGN_OPEN if an undecided admissible
+ *             interval has [LO, HI] meeting [target - W, target + W]; else
+ *             SST_ALIGN_NONE.
+ *   n_fit     the split-closed admissible intervals that hold a fitting sum
+ *             (the fragment's closed intervals hold none, or it would not have
+ *             been OPEN).
+ *   first     l << 8 | r of the smallest of them, else 0xFFFE.
+ *   alignable 0 for NONE, else 1.
+ * Every other fragment keeps all four outputs bit for bit; in particular the
+ * n_fit of a fragment that was FIT before still counts closed intervals only.
+ * The call is idempotent on its own output.  A split NONE is as safe as a
+ * base NONE: no achievable sum of any admissible interval fits, and that was
+ * enumerated exactly.
+ * One kernel (k_align_split, sst_align.hip) queued on the ctx stream, so it
+ * follows sst_align_windows_device without a host round trip; spectra without
+ * an OPEN fragment cost one read of their status bytes; no scratch buffer, no
+ * global atomics.  Argument checks and errors as sst_align_windows_device. */
+int sst_align_split_device(sst_table* t, const sst_align_args* a);
+
 /* compute_sequence_length_bound (mass_table.py:343-487) after the skeleton's
  * alphabet reduction (skeleton_building.py:315-336), both directions, for
  * queries on per-spectrum reduced alphabets, exact without a table rebuild:
@@ -1123,6 +1158,7 @@ int64_t sst_pyset_order(const int32_t* keys, const int64_t* hashes, int64_t n, i
 #define SST_K_HANDOFF 19 /* k_handoff_count + k_scan_u32, k_handoff_emit (sst_handoff_*_device) */
 #define SST_K_TABLE_CERTIFY 20 /* k_table_certify (sst_table_certify) */
 #define SST_K_ALIGN 21 /* k_align_windows (sst_align_windows_device) */
+#define SST_K_ALIGN_SPLIT 22 /* k_align_split (sst_align_split_device) */
 #define SST_K_COUNT 24
 /* When enabled, every kernel launch of this ctx is bracketed by hipEvents
  * recorded on the ctx stream; sst_profile_read synchronises and returns the

@@ -39,7 +39,7 @@ EXPORTS = (
     "sst_dict_list_device", "sst_fix_finish_device", "sst_pipe_reserve_rows", "sst_reach_lowest_device",
     "sst_length_bounds_frontier_device", "sst_post_skeleton_device", "sst_ctx_trim", "sst_requery_merge_device",
     "sst_handoff_count_device", "sst_handoff_emit_device", "sst_table_scan_lds_hits", "sst_table_certify",
-    "sst_align_capacity", "sst_align_windows_device",
+    "sst_align_capacity", "sst_align_windows_device", "sst_align_split_device",
 )
 
 # kernel ids of sst_profile_read
@@ -49,6 +49,7 @@ K_RESULT_PACK = 6
  K_LENGTH_BOUND, K_JACCARD, K_PAIRS_ALPHA, K_REQUERY_MERGE, K_HANDOFF) = range(7, 20)
 K_TABLE_CERTIFY = 20
 K_ALIGN = 21
+K_ALIGN_SPLIT = 22
 K_COUNT = 24  # SST_K_COUNT
 KERNEL_NAMES = {K_IS_VALID: "k_is_valid", K_EXPLAIN_SCAN: "k_explain_scan", K_EXPLAIN_DEEP: "k_explain_deferred",
                 K_EXPLAIN_EXPAND: "k_explain_expand",
@@ -57,7 +58,8 @@ KERNEL_NAMES = {K_IS_VALID: "k_is_valid", K_EXPLAIN_SCAN: "k_explain_scan", K_EX
                 K_BINS_COUNT: "k_bins_count", K_BINS_EMIT: "k_bins_emit", K_DICT: "k_dict_build",
                 K_SKEL_WALK: "k_skel_walk", K_REACH_ROWS: "k_reach_rows", K_LENGTH_BOUND: "k_length_bound",
                 K_JACCARD: "k_jaccard", K_PAIRS_ALPHA: "k_pairs_alpha", K_REQUERY_MERGE: "k_requery_merge",
-                K_HANDOFF: "k_handoff", K_TABLE_CERTIFY: "k_table_certify", K_ALIGN: "k_align_windows"}
+                K_HANDOFF: "k_handoff", K_TABLE_CERTIFY: "k_table_certify", K_ALIGN: "k_align_windows",
+                K_ALIGN_SPLIT: "k_align_split"}
 
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
@@ -341,6 +343,8 @@ def load_library(path=LIB_PATH):
     lib.sst_align_capacity.restype = ctypes.c_uint32
     lib.sst_align_windows_device.argtypes = [_P, ctypes.POINTER(AlignArgs)]
     lib.sst_align_windows_device.restype = _I
+    lib.sst_align_split_device.argtypes = [_P, ctypes.POINTER(AlignArgs)]
+    lib.sst_align_split_device.restype = _I
     lib.sst_jaccard_device.argtypes = [_P, ctypes.POINTER(JaccardArgs)]
     lib.sst_jaccard_device.restype = _I
     lib.sst_skeleton_alpha_device.argtypes = [_P, _I64, _P, _P, _P, _P, _P]

@@ -11,6 +11,10 @@ can be skipped; alignable == 1 promises nothing.
 align_host is the definition in plain numpy / Python (the mirror for spectra
 run_batch routed to the host, and the model the tests hold the kernel to),
 align_device the kernel (csrc/sst_align.hip) over a whole outcome.
+
+split=True (both) also decides the open intervals that cut into two closed
+halves, a fitting sum searched as a + b over the halves' sorted lists
+(sst_align_split_device); only fragments that are OPEN without it change.
 """
 import ctypes
 import math
@@ -106,7 +110,7 @@ def position_sets(skeleton, alpha, n_rows):
     return out
 
 
-def _align_spectrum(L, sets, row_mass, code, su, obs, mn, mx, tolerance, precision, capacity):
+def _align_spectrum(L, sets, row_mass, code, su, obs, mn, mx, tolerance, precision, capacity, split=False):
     n = len(code)
     status = np.zeros(n, np.uint8)
     n_fit = np.zeros(n, np.int64)
@@ -164,13 +168,73 @@ def _align_spectrum(L, sets, row_mass, code, su, obs, mn, mx, tolerance, precisi
         sweep(L - 1, -1, lambda l, r: (cls == 2) & (l >= lo_end) & (l <= mn))
 
     status[:] = np.where(skipped, ALIGN_SKIPPED, np.where(n_fit > 0, ALIGN_FIT, np.where(opened, ALIGN_OPEN, ALIGN_NONE)))
+    todo = status == ALIGN_OPEN
+    if not split or not todo.any():
+        return status, n_fit, np.where(n_fit > 0, first, NO_INTERVAL)
+
+    # the split: the base-OPEN fragments again, over the open intervals only
+    opened[:] = False
+    last = int(fhi[todo].max())
+
+    def split_sweep(start, step, ok_of):
+        a, lo_a, hi_a = np.zeros(1, np.int64), 0, 0  # S(start, m*), the last closed interval of the sweep
+        p = start
+        while 0 <= p < L:
+            m = masses[p]
+            if lo_a + int(m[0]) > last:
+                return
+            nxt = np.unique(np.add.outer(a, m)) if len(m) > 1 else a + m[0]
+            if len(nxt) > capacity:
+                break
+            a, lo_a, hi_a = nxt, lo_a + int(m[0]), hi_a + int(m[-1])
+            p += step
+        else:
+            return  # every interval of the sweep is closed
+        halves = p != start  # (else not even one position is closed: nothing splits)
+        b, LO, HI = np.zeros(1, np.int64), lo_a, hi_a
+        while 0 <= p < L:
+            m = masses[p]
+            LO, HI = LO + int(m[0]), HI + int(m[-1])
+            if LO > last:
+                break
+            if halves and b is not None:
+                b = np.unique(np.add.outer(b, m)) if len(m) > 1 else b + m[0]
+                if len(b) > capacity:
+                    b = None  # undecided from here on
+            l, r = (start, p) if step > 0 else (p, start)
+            cand = np.flatnonzero(ok_of(l, r) & todo & (fhi >= LO) & (flo <= HI))
+            if not halves or b is None:
+                opened[cand] = True
+            else:
+                for j in cand:
+                    x = a[(a >= flo[j] - b[-1]) & (a <= fhi[j] - b[0])]
+                    at = np.searchsorted(b, flo[j] - x, side="left")
+                    if ((at < len(b)) & (b[np.minimum(at, len(b) - 1)] <= fhi[j] - x)).any():
+                        n_fit[j] += 1
+                        first[j] = min(first[j], l << 8 | r)
+            p += step
+
+    for l in range(L if (internal & todo).any() else min(L, 1)):
+        if l == 0:
+            split_sweep(0, 1, lambda l, r: internal | ((cls == 1) & (r >= lo_end) & (r <= mx)) | ((cls == 3) & (r == L - 1)))
+        else:
+            split_sweep(l, 1, lambda l, r: internal)
+    if ((cls == 2) & todo).any():
+        split_sweep(L - 1, -1, lambda l, r: (cls == 2) & (l >= lo_end) & (l <= mn))
+    status[todo] = np.where(n_fit[todo] > 0, ALIGN_FIT, np.where(opened[todo], ALIGN_OPEN, ALIGN_NONE))
     return status, n_fit, np.where(n_fit > 0, first, NO_INTERVAL)
 
 
-def align_host(outcome, tolerance, precision, capacity=ALIGN_CAPACITY):
+def align_host(outcome, tolerance, precision, capacity=ALIGN_CAPACITY, split=False):
     """The certificate of every fragment of `outcome` (a BatchOutcome), by the
     definition: per left end the achievable sums of the growing interval as a
-    sorted array, open once they number more than `capacity`."""
+    sorted array, open once they number more than `capacity`.
+    split=True: the fragments that are OPEN by that are decided again over
+    the open intervals (include/sst.h, sst_align_split_device): an open
+    interval whose greedy first half and the rest are both closed holds a
+    fitting sum iff some a + b of the halves' sums fits; where the rest is
+    open too the interval is undecided, as every open one is without split.
+    The other fragments keep their outputs."""
     S, nf = len(outcome), int(outcome.frag_off[-1])
     status = np.zeros(nf, np.uint8)
     n_fit = np.zeros(nf, np.uint32)
@@ -193,26 +257,28 @@ def align_host(outcome, tolerance, precision, capacity=ALIGN_CAPACITY):
             continue
         st, nn, ff = _align_spectrum(L, sets, outcome.row_mass, outcome.frag_code[f], outcome.frag_su[f],
                                      outcome.frag_obs[f], outcome.frag_min_end[f].astype(np.int64),
-                                     outcome.frag_max_end[f].astype(np.int64), tolerance, precision, int(capacity))
+                                     outcome.frag_max_end[f].astype(np.int64), tolerance, precision, int(capacity),
+                                     split)
         status[f], n_fit[f], first[f] = st, nn, ff
     alignable = ((status != ALIGN_NONE) & (status != ALIGN_INFEASIBLE)).astype(np.uint8)
     return AlignOutcome(frag_off=outcome.frag_off.copy(), status=status, alignable=alignable, n_fit=n_fit, first=first)
 
 
-def align_device(dp_table, outcome):
+def align_device(dp_table, outcome, split=False):
     """The certificate of every fragment of `outcome` on dp_table's device
     (sst_align_windows_device, capacity sst_align_capacity()): one upload per
     input array, one launch, one download per output array.  `outcome` must be
-    on dp_table's rows."""
+    on dp_table's rows.  split=True: sst_align_split_device follows on the
+    same stream before the one download (align_host's split=True)."""
     from .pipeline_device import _one_stream
 
     masses = [int(m.mass) for m in dp_table.masses]
     if masses != [int(x) for x in outcome.row_mass]:
         raise ValueError("align_device: the outcome is not on this table's rows")
-    return _one_stream(_align_device)(dp_table, outcome)
+    return _one_stream(_align_device)(dp_table, outcome, split)
 
 
-def _align_device(dp_table, o):
+def _align_device(dp_table, o, split=False):
     import torch
 
     dt = dp_table.device_table
@@ -243,6 +309,8 @@ def _align_device(dp_table, o):
     a.status, a.alignable, a.n_fit, a.first = (x.data_ptr() for x in (status, alignable, n_fit, first))
     torch.cuda.synchronize(dev)
     eng.check(eng._lib.sst_align_windows_device(dt.handle, ctypes.byref(a)), "sst_align_windows_device")
+    if split:
+        eng.check(eng._lib.sst_align_split_device(dt.handle, ctypes.byref(a)), "sst_align_split_device")
     eng.synchronize()
     return AlignOutcome(frag_off=o.frag_off.copy(), status=status.cpu().numpy(), alignable=alignable.cpu().numpy(),
                         n_fit=n_fit.cpu().numpy().view(np.uint32), first=first.cpu().numpy().view(np.uint16))

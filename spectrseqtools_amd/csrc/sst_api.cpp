@@ -3749,7 +3749,8 @@ extern "C" int sst_handoff_emit_device(sst_table* t, const sst_handoff_args* a) 
 
 extern "C" uint32_t sst_align_capacity(void) { return SST_ALIGN_CAPACITY; }
 
-extern "C" int sst_align_windows_device(sst_table* t, const sst_align_args* a) {
+// 1: launch; SST_OK: nothing to do; else the error (both alignment entry points)
+static int align_args_check(const sst_table* t, const sst_align_args* a) {
   if (!t || !a || a->n_spec < 0 || a->n_spec > INT32_MAX) return SST_E_ARG;
   if (!std::isfinite(a->tol) || !std::isfinite(a->prec) || !(a->prec > 0)) return SST_E_ARG;
   if (a->n_spec == 0) return SST_OK;
@@ -3759,11 +3760,26 @@ extern "C" int sst_align_windows_device(sst_table* t, const sst_align_args* a) {
   if (t->n_rows > SST_MAX_ROWS) return SST_E_ARG;
   for (int r = 0; r < t->n_rows; ++r)  // sums of 253 positions stay below 2^32
     if (t->masses[r] < 0 || t->masses[r] >= (int64_t)(0x100000000ull / 253)) return SST_E_ARG;
+  return 1;
+}
+
+extern "C" int sst_align_windows_device(sst_table* t, const sst_align_args* a) {
+  if (int rc = align_args_check(t, a); rc != 1) return rc;
   sst_ctx* c = t->ctx;
   std::lock_guard<std::recursive_mutex> g(c->mu);
   if (int rc = set_device(c)) return rc;
   Prof p(c, SST_K_ALIGN);
   HIP_OK(c, sst::launch_align_windows(*a, t->args.w, t->n_rows, 2 * c->n_cu, c->stream));
+  return SST_OK;
+}
+
+extern "C" int sst_align_split_device(sst_table* t, const sst_align_args* a) {
+  if (int rc = align_args_check(t, a); rc != 1) return rc;
+  sst_ctx* c = t->ctx;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  if (int rc = set_device(c)) return rc;
+  Prof p(c, SST_K_ALIGN_SPLIT);
+  HIP_OK(c, sst::launch_align_split(*a, t->args.w, t->n_rows, 2 * c->n_cu, c->stream));
   return SST_OK;
 }
 

@@ -50,7 +50,7 @@ GPU-busy share of its wall time.
 
 Usage: python tools/pipeline_bench.py [--spectra 100000] [--seed 7] [--host-driven]
        [--backend nccl|gloo] [--dump-outcomes DIR] [--as-rank R] [--handoff [--handoff-repeats 3]]
-       [--align]
+       [--align | --align-split]
 """
 import argparse
 import json
@@ -272,13 +272,45 @@ def handoff_timings(pd, dp, rows, ln, post, repeats):
                                      "downloaded whole, compacted with numpy"}}
 
 
-def align_stage(pd, dp, rows, ln, post, kernels):
+def position_rows(out):
+    """|A_i| of every position of a BatchOutcome (alignment.position_sets'
+    rule: P_i & alpha where P_i != 0, else alpha; row 0 excluded), and which
+    positions are unconstrained (an all-zero mask)."""
+    spec = np.repeat(np.arange(len(out.seq_len)), np.diff(out.pos_off))
+    free = (out.skeleton[:, 0] | out.skeleton[:, 1]) == 0
+    n = np.zeros(len(spec), np.int64)
+    for w in (0, 1):
+        a = out.alpha[spec, w]
+        m = np.where(free, a, out.skeleton[:, w] & a) & (~np.uint64(1) if w == 0 else ~np.uint64(0))
+        n += np.unpackbits(np.ascontiguousarray(m).view(np.uint8)).reshape(-1, 64).sum(axis=1, dtype=np.int64)
+    return n, free
+
+
+def unconstrained_runs(out, spectra, free=None):
+    """Per spectrum of `spectra`: its longest run of unconstrained positions
+    (an all-zero position mask: the whole alphabet) and their number."""
+    free = (out.skeleton[:, 0] | out.skeleton[:, 1]) == 0 if free is None else free
+    longest, count = [], []
+    for g in spectra.tolist():
+        f = free[int(out.pos_off[g]):int(out.pos_off[g + 1])]
+        edge = np.flatnonzero(np.diff(np.concatenate([[0], f.view(np.int8), [0]])))
+        longest.append(int((edge[1::2] - edge[::2]).max()) if len(edge) else 0)
+        count.append(int(f.sum()))
+    return np.array(longest, dtype=np.int64), np.array(count, dtype=np.int64)
+
+
+def align_stage(pd, dp, rows, ln, post, kernels, split=False):
     """--align: the alignment certificate (alignment.align_device) over the
     hand-off of the spectra the stages ran -- wall seconds from the host
     arrays in to the host arrays out (uploads, k_align_windows, downloads), the
     kernel's event time, and the share of each status over all fragments.
-    The hand-off itself is not part of the time."""
-    from spectrseqtools_amd import alignment
+    The hand-off itself is not part of the time.
+    --align-split (split=True): the timed call is align_device(split=True)
+    (k_align_split follows k_align_windows on the stream, one download); the
+    base certificate is then taken again, untimed, for the shares before the
+    split, what became of the base-OPEN fragments, and what the spectra that
+    are still OPEN look like."""
+    from spectrseqtools_amd import _native, alignment
 
     S = len(ln.seq_len)
     act = np.asarray(post.active[:S]) != 0
@@ -292,16 +324,57 @@ def align_stage(pd, dp, rows, ln, post, kernels):
                           breakage_names=rows.names, row_names=empty.row_names, row_mass=empty.row_mass)
     kernels()  # (the hand-off's launches are not this stage's)
     t0 = time.perf_counter()
-    al = alignment.align_device(dp, out)
+    al = alignment.align_device(dp, out, split=split)
     s = time.perf_counter() - t0
+    kern = kernels()
     n = np.diff(out.frag_off)
     internal = (out.frag_code >> 2) & 3 == 0
-    return {"s": s, "spectra": int(act.sum()), "fragments": int(out.frag_off[-1]), "positions": int(out.pos_off[-1]),
-            "fragments_per_spectrum_max": int(n.max()) if S else 0, "seq_len_max": int(out.seq_len.max()) if S else 0,
-            "internal_fragments": int(internal.sum()), "capacity": alignment.ALIGN_CAPACITY,
-            "status_shares": al.shares(), "not_alignable_share": float(1.0 - al.alignable.mean()) if len(al.status) else 0.0,
-            "not_alignable_share_internal": float(1.0 - al.alignable[internal].mean()) if internal.any() else 0.0,
-            "path": "device (sst_align_windows_device), host arrays in and out", "kernels": kernels()}
+    rec = {"s": s, "spectra": int(act.sum()), "fragments": int(out.frag_off[-1]), "positions": int(out.pos_off[-1]),
+           "fragments_per_spectrum_max": int(n.max()) if S else 0, "seq_len_max": int(out.seq_len.max()) if S else 0,
+           "internal_fragments": int(internal.sum()), "capacity": alignment.ALIGN_CAPACITY,
+           "status_shares": al.shares(), "not_alignable_share": float(1.0 - al.alignable.mean()) if len(al.status) else 0.0,
+           "not_alignable_share_internal": float(1.0 - al.alignable[internal].mean()) if internal.any() else 0.0,
+           "path": "device (sst_align_windows_device), host arrays in and out", "kernels": kern}
+    if not split:
+        return rec
+    base = alignment.align_device(dp, out)  # untimed: what the split started from
+    kernels()
+    was_open = base.status == _native.ALIGN_OPEN
+    still = al.status == _native.ALIGN_OPEN
+    n_open = max(1, int(was_open.sum()))
+    spec_of = np.repeat(np.arange(S), n)
+    pct = lambda x: {str(p): float(np.percentile(x, p)) for p in (50, 90, 99, 100)} if len(x) else {}  # noqa: E731
+    rows_of = lambda g: np.array([bin(int(a0)).count("1") + bin(int(a1)).count("1") for a0, a1 in out.alpha[g]])  # noqa: E731
+
+    n_rows, free = position_rows(out)
+
+    def describe(mask):  # the spectra that hold a fragment of `mask`
+        g = np.unique(spec_of[mask])
+        longest, count = unconstrained_runs(out, g, free)
+        per = [n_rows[int(out.pos_off[x]):int(out.pos_off[x + 1])] for x in g.tolist()]
+        return {"spectra": int(len(g)), "fragments": int(mask.sum()), "seq_len": pct(out.seq_len[g]),
+                "alphabet_rows": pct(rows_of(g)), "unconstrained_positions": pct(count),
+                "longest_unconstrained_run": pct(longest),
+                "rows_per_position_mean": pct([float(x.mean()) for x in per if len(x)]),
+                "rows_per_position_max": pct([int(x.max()) for x in per if len(x)]),
+                "positions_of_several_rows": pct([int((x > 1).sum()) for x in per]),
+                # log2 of the product of |A_i| over the whole skeleton: the sums [0, L - 1] could have at most
+                "log2_combinations": pct([float(np.log2(np.maximum(x, 1)).sum()) for x in per])}
+
+    unchanged = all(np.array_equal(getattr(al, k)[~was_open], getattr(base, k)[~was_open]) for k in al.FRAGMENT_FIELDS)
+    rec.update({"path": "device (sst_align_windows_device + sst_align_split_device), host arrays in and out",
+                "status_shares_base": base.shares(),
+                "open_decided_share": float((was_open & ~still).sum()) / n_open,
+                "open_to_fit_share": float((was_open & (al.status == _native.ALIGN_FIT)).sum()) / n_open,
+                "open_to_none_share": float((was_open & (al.status == _native.ALIGN_NONE)).sum()) / n_open,
+                "none_share_added": float((was_open & (al.status == _native.ALIGN_NONE)).sum()) / max(1, len(al.status)),
+                "not_alignable_share_base": float(1.0 - base.alignable.mean()) if len(base.status) else 0.0,
+                "other_fragments_unchanged": bool(unchanged),
+                "kernel_ms": {str(k): kern.get(_native.KERNEL_NAMES[k], (0.0, 0))[0]
+                              for k in (_native.K_ALIGN, _native.K_ALIGN_SPLIT)},
+                "split_spectra": describe(was_open),  # the spectra k_align_split swept (a base-OPEN fragment)
+                "open_after_split": describe(still)})
+    return rec
 
 
 def main():
@@ -340,9 +413,15 @@ def main():
     ap.add_argument("--align", action="store_true",
                     help="after the stages, also run the alignment certificate (alignment.align_device) over the "
                          "hand-off: a stage \"align\" with its seconds and the share of each status over all fragments")
+    ap.add_argument("--align-split", action="store_true",
+                    help="--align with the two-list split of the open intervals (align_device(split=True)): the "
+                         "stage also reports the shares before the split, the share of the base-OPEN fragments it "
+                         "decides (open_decided_share) and turns into NONE (open_to_none_share), each kernel's "
+                         "milliseconds, and what the spectra that stay OPEN look like")
     ap.add_argument("--as-rank", type=int, default=None,
                     help="single process: generate the spectra rank R of a multi-rank run would get")
     args = ap.parse_args()
+    args.align = args.align or args.align_split
 
     import torch
 
@@ -436,7 +515,7 @@ def main():
         lw = pd.length_device(dp, kw, bw.alpha_dev, su_seq[:S0], batch.seq_mass[:S0], trim=False)
         pw = pd.post_skeleton_device(dp, rw, kw, lw)
         if args.align:
-            align_stage(pd, dp, rw, lw, pw, lambda: None)
+            align_stage(pd, dp, rw, lw, pw, lambda: {}, split=args.align_split)
         # the reach buffer at length_device's batch budget, as a serving
         # process holds it: the timed stage allocates nothing (its hipMalloc /
         # hipFree of tens of GB took 0.1-3 s from run to run)
@@ -604,7 +683,7 @@ def main():
                                     + (f" ({'RCCL' if args.backend == 'nccl' else 'gloo'})" if dist else " (local)")}
     if rows is not None and args.align:
         barrier()
-        stages["align"] = align_stage(pd, dp, rows, ln, post, kernels)
+        stages["align"] = align_stage(pd, dp, rows, ln, post, kernels, split=args.align_split)
         stages["align"]["s"] = tmax(stages["align"]["s"])
         busy(stages["align"])
         progress("align")
