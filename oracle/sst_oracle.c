@@ -624,6 +624,62 @@ int64_t ora_explain_batch(const void* table, int nrows, int64_t cols, int C, con
     return tot;
 }
 
+/* One (position, byte) term of a list digest: the splitmix64 finaliser of
+ * (position << 8 | byte).  A list's digest is the sum of its terms mod 2^64, so
+ * it depends on every byte and on where it stands, and a test can compute it
+ * for all queries of a result at once (tests/_digest.py restates it in numpy). */
+static inline uint64_t digest_term(uint64_t pos, uint8_t byte) {
+    uint64_t z = ((pos << 8) | byte) + 0x9e3779b97f4a7c15ull;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
+/* ora_explain_batch with the lists collected: per query its status, candidate
+ * count, and the byte length and digest of the list written as the engine's
+ * payload writes it -- the candidates in ora_explain_table's order, each as
+ * [k][its k row indices, ascending], one byte per field.  nbytes[i] = -1 (and
+ * digest 0) where a candidate does not fit that format (k or a row > 255).
+ * Returns the sum of the counts. */
+int64_t ora_explain_digest_batch(const void* table, int nrows, int64_t cols, int C, const int64_t* w,
+                                 const uint8_t* is_mod, const int64_t* cap, const double* mass, const double* thr,
+                                 const int64_t* A, int64_t n, double tolerance, double precision, int with_memo,
+                                 int nthreads, int8_t* status, int64_t* count, int64_t* nbytes, uint64_t* digest) {
+    int64_t tot = 0;
+#ifdef _OPENMP
+    if (nthreads > 0) omp_set_num_threads(nthreads);
+#pragma omp parallel for schedule(dynamic, 16) reduction(+ : tot)
+#endif
+    for (int64_t i = 0; i < n; i++) {
+        ora_result r;
+        ora_explain_table(table, nrows, cols, C, w, is_mod, cap, mass[i], thr ? thr[i] : NAN, tolerance, precision,
+                          A[i], with_memo, 1, &r);
+        uint64_t h = 0, pos = 0;
+        int fits = 1;
+        if (r.status == 1) {
+            int64_t p = 0;
+            for (int64_t s = 0; s < r.n_solutions && fits; s++) {
+                const int32_t k = r.lens[s];
+                if (k > 255) fits = 0;
+                h += digest_term(pos++, (uint8_t)k);
+                for (int32_t j = 0; j < k && fits; j++) {
+                    const int16_t row = r.rows[p + j];
+                    if (row < 0 || row > 255) fits = 0;
+                    h += digest_term(pos++, (uint8_t)row);
+                }
+                p += k;
+            }
+        }
+        status[i] = (int8_t)r.status;
+        count[i] = r.n_solutions;
+        nbytes[i] = fits ? (int64_t)pos : -1;
+        digest[i] = fits ? h : 0;
+        tot += r.n_solutions;
+        ora_result_free(&r); /* (a raise leaves both pointers NULL) */
+    }
+    return tot;
+}
+
 int ora_num_threads(void) {
 #ifdef _OPENMP
     return omp_get_max_threads();

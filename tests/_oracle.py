@@ -50,6 +50,8 @@ def _load():
     lib.ora_is_valid_batch.argtypes = [P, I, I64, I, P, P, I64, D, D, I, P]
     lib.ora_explain_batch.restype = I64
     lib.ora_explain_batch.argtypes = [P, I, I64, I, P, P, P, P, P, P, I64, D, D, I, I, P, P, P]
+    lib.ora_explain_digest_batch.restype = I64
+    lib.ora_explain_digest_batch.argtypes = [P, I, I64, I, P, P, P, P, P, P, I64, D, D, I, I, P, P, P, P]
     lib.ora_num_threads.restype = I
     return lib
 
@@ -154,6 +156,25 @@ def explain_batch(table, C, alph, masses, thrs, A, tolerance, with_memo=True, nt
                           _p(masses), _p(thrs), _p(Aa), n, float(tolerance), float(precision), int(with_memo),
                           int(nthreads), _p(st), _p(cnt), _p(lk))
     return st, cnt, lk
+
+
+def explain_digest_batch(table, C, alph, masses, thrs, A, tolerance, with_memo=True, nthreads=1, precision=1e-3):
+    """explain_batch with the lists collected -> (status, count, nbytes,
+    digest) per query: the byte length and the 64-bit order-sensitive digest
+    (tests/_digest.py) of the query's candidate list in the engine's payload
+    format, candidates in explain_table's order, each [k][k rows ascending]."""
+    n = len(masses)
+    masses = np.ascontiguousarray(masses, dtype=np.float64)
+    thrs = None if thrs is None else np.ascontiguousarray(thrs, dtype=np.float64)
+    Aa = np.ascontiguousarray(np.broadcast_to(np.asarray(A, dtype=np.int64), (n,)))
+    st = np.zeros(n, np.int8)
+    cnt = np.zeros(n, np.int64)
+    nb = np.zeros(n, np.int64)
+    dg = np.zeros(n, np.uint64)
+    LIB.ora_explain_digest_batch(_p(table), table.shape[0], table.shape[1], C, _p(alph.w), _p(alph.is_mod),
+                                 _p(alph.cap), _p(masses), _p(thrs), _p(Aa), n, float(tolerance), float(precision),
+                                 int(with_memo), int(nthreads), _p(st), _p(cnt), _p(nb), _p(dg))
+    return st, cnt, nb, dg
 
 
 def is_valid_batch(table, C, masses, thrs, tolerance, nthreads=1, precision=1e-3):

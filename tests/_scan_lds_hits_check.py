@@ -5,7 +5,8 @@ sst_step_device or sst_explain_batch_device and writes, per case, SHA-256
 digests of the result's parts and what the wave's hit counts say about the
 capacity in force, as JSON to the path given.  With --reference (the K = 0
 run) each step case is also compared per query with the two separate calls
-and a sample with the CPU oracle."""
+and a sample with the CPU oracle's lists, and every case's every query with
+the oracle's status, count and list digest."""
 import hashlib
 import json
 import os
@@ -165,6 +166,7 @@ def run_case(eng, dev, rows, host, alph, case, K, reference):
             assert int(res.status[i]) == want, (name, i)
             if sols:
                 assert res.candidates(int(i)) == sols, (name, i)
+        S.check_vs_oracle(res, (host, alph), masses, thr, None, name)
     res.close()
     return out
 

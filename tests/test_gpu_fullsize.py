@@ -1,8 +1,9 @@
 """Full-size parity at the benchmark's workload (10 000
 synthetic spectra, full alphabet, <= 20-mer; 4.3 M A7 + 10.7 M A8 queries):
 is_valid and explain statuses / candidate counts against the OpenMP C
-oracle, bit-exact, and every returned candidate checked by size-independent
-properties (a distinct multiset of table rows, in the reference's order,
+oracle, bit-exact, every query's exact candidate list against the oracle's
+by byte length and digest, and every returned candidate checked by
+size-independent properties (a distinct multiset of table rows, in the reference's order,
 whose mass sum lies in the query's quantised window)."""
 import os
 import sys
@@ -10,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 
+import _digest
 import _oracle as oracle
 
 pytestmark = pytest.mark.gpu
@@ -34,7 +36,8 @@ def fullsize():
 @pytest.fixture(scope="module")
 def oracle_a8(fullsize):
     """The C oracle's statuses / counts for all A8 queries (OpenMP), mapped
-    to the engine's status codes; computed once for the module."""
+    to the engine's status codes, and the byte length and digest of every
+    query's candidate list; computed once for the module."""
     from spectrseqtools_amd import _native
 
     dp, wl = fullsize
@@ -43,10 +46,21 @@ def oracle_a8(fullsize):
     alph = oracle.Alphabet(ms, [m.is_modification for m in dp.masses],
                            [round(dp.seq.max_len * m.modification_rate) for m in dp.masses])
     A = round(dp.seq.modification_rate * dp.seq.max_len)
-    ost, ocnt, _ = oracle.explain_batch(host, 32, alph, wl["a8_mass"], wl["a8_thr"], A, dp.tolerance, nthreads=16)
-    want = np.where(ost < 0, _native.SST_OUT_OF_TABLE,
-                    np.where(ost == 0, _native.SST_NONE, np.where(ocnt > 0, _native.SST_SOME, _native.SST_EMPTY)))
-    return host, alph, want, ocnt
+    ost, ocnt, onb, odg = oracle.explain_digest_batch(host, 32, alph, wl["a8_mass"], wl["a8_thr"], A, dp.tolerance,
+                                                      nthreads=16)
+    want = _digest.engine_status(ost, ocnt, _native)
+    return host, alph, want, ocnt, (ost, ocnt, onb, odg)
+
+
+def _check_lists(res, fullsize, oracle_a8, what):
+    """Every SOME query's exact list against the oracle's (length, digest)."""
+    from spectrseqtools_amd import _native
+
+    dp, wl = fullsize
+    host, alph, _, _, dig = oracle_a8
+    A = round(dp.seq.modification_rate * dp.seq.max_len)
+    one = lambda i: oracle.explain_table(host, 32, alph, wl["a8_mass"][i], wl["a8_thr"][i], dp.tolerance, A)[1]
+    assert _digest.assert_equals_oracle(res, dig, one, _native, what) > 1_000_000
 
 
 def _check_candidates(res, masses, thr, ms, prec):
@@ -95,7 +109,7 @@ def test_fullsize_explain_vs_oracle_and_properties(fullsize, oracle_a8):
     from spectrseqtools_amd import _native
 
     dp, wl = fullsize
-    host, alph, want, ocnt = oracle_a8
+    host, alph, want, ocnt, _ = oracle_a8
     ms = np.array([m.mass for m in dp.masses], dtype=np.int64)
     A = round(dp.seq.modification_rate * dp.seq.max_len)
     masses, thr = wl["a8_mass"], wl["a8_thr"]
@@ -106,6 +120,7 @@ def test_fullsize_explain_vs_oracle_and_properties(fullsize, oracle_a8):
     some = res.status == _native.SST_SOME
     assert np.array_equal(res.count[some].astype(np.int64), ocnt[some])
     _check_candidates(res, masses, thr, ms, dp.precision)
+    _check_lists(res, fullsize, oracle_a8, "explain")
 
 
 def test_fullsize_device_path_reused_vs_oracle(fullsize, oracle_a8):
@@ -141,10 +156,11 @@ def test_fullsize_device_path_reused_vs_oracle(fullsize, oracle_a8):
         assert len(res.payload) == n_bytes
         digests.append((res.status.tobytes(), recs.tobytes(), res.payload.tobytes()))
     assert digests[0] == digests[1]
-    host, alph, want, ocnt = oracle_a8
+    host, alph, want, ocnt, _ = oracle_a8
     assert np.array_equal(res.status.astype(np.int64), want)
     some = res.status == _native.SST_SOME
     assert np.array_equal(res.count[some].astype(np.int64), ocnt[some])
+    _check_lists(res, fullsize, oracle_a8, "explain_device")
     # the hit list: one record per query with candidates, decoding to the
     # fetched count / offset arrays; payloads in hit order, back to back
     q = recs[:, 0].astype(np.int64)
@@ -172,15 +188,15 @@ def test_fullsize_step_device_vs_oracle(fullsize, oracle_a8):
     k_step, one scan workgroup per CU, ~41 tile rounds per scan wave, the
     is_valid workgroups beside it -- on the full config-3 workload, twice into
     one reused result.  Against the oracle: the A7 byte of every (peak x
-    breakage) pair, every A8 status and count, the exact candidate lists of a
-    sample, the candidates' properties for all queries, the dense hit list and
+    breakage) pair, every A8 status and count, the exact candidate lists of all
+    queries (digests), the candidates' properties for all queries, the dense hit list and
     the wire-v5 decode of the pass (scan order, pair refs)."""
     torch = pytest.importorskip("torch")
     from spectrseqtools_amd import _native
     from spectrseqtools_amd.parallel import canonical_digest, decode_hits, device_bytes, scan_order_key, wire_unpack
 
     dp, wl = fullsize
-    host, alph, want, ocnt = oracle_a8
+    host, alph, want, ocnt, _ = oracle_a8
     ms = np.array([m.mass for m in dp.masses], dtype=np.int64)
     A = round(dp.seq.modification_rate * dp.seq.max_len)
     masses, thr = wl["a8_mass"], wl["a8_thr"]
@@ -217,9 +233,10 @@ def test_fullsize_step_device_vs_oracle(fullsize, oracle_a8):
     some = res.status == _native.SST_SOME
     assert np.array_equal(res.count[some].astype(np.int64), ocnt[some])
     _check_candidates(res, masses, thr, ms, dp.precision)
-    # exact candidate lists (reference order) of a sample of the hits
+    # exact candidate lists (reference order) of all hits, and of a few through the per-query accessor
+    _check_lists(res, fullsize, oracle_a8, "step_device")
     rng = np.random.default_rng(31)
-    for i in rng.choice(np.flatnonzero(some), 3000, replace=False):
+    for i in rng.choice(np.flatnonzero(some), 50, replace=False):
         st, sols, _, _ = oracle.explain_table(host, 32, alph, masses[i], thr[i], dp.tolerance, A)
         assert res.candidates(int(i)) == sols, i
     # the dense hit list: pair-path hits first, in the scan's order
@@ -251,13 +268,13 @@ def test_fullsize_rows_step_vs_oracle(fullsize, oracle_a8):
     reused result.  Its queries are the host producers' in the same order, so
     against the oracle: the A7 byte of every (peak x breakage) pair, every A8
     status and count, the candidates' properties, the exact candidate lists of
-    a sample and the dense hit list (query order, payload back to back)."""
+    all queries (digests) and the dense hit list (query order, payload back to back)."""
     torch = pytest.importorskip("torch")
     from spectrseqtools_amd import _native
     from spectrseqtools_amd.parallel import device_bytes
 
     dp, wl = fullsize
-    host, alph, want, ocnt = oracle_a8
+    host, alph, want, ocnt, _ = oracle_a8
     ms = np.array([m.mass for m in dp.masses], dtype=np.int64)
     A = round(dp.seq.modification_rate * dp.seq.max_len)
     masses, thr = wl["a8_mass"], wl["a8_thr"]
@@ -290,8 +307,9 @@ def test_fullsize_rows_step_vs_oracle(fullsize, oracle_a8):
     some = res.status == _native.SST_SOME
     assert np.array_equal(res.count[some].astype(np.int64), ocnt[some])
     _check_candidates(res, masses, thr, ms, dp.precision)
+    _check_lists(res, fullsize, oracle_a8, "step_rows_device")
     rng = np.random.default_rng(37)
-    for i in rng.choice(np.flatnonzero(some), 3000, replace=False):
+    for i in rng.choice(np.flatnonzero(some), 50, replace=False):
         st, sols, _, _ = oracle.explain_table(host, 32, alph, masses[i], thr[i], dp.tolerance, A)
         assert res.candidates(int(i)) == sols, i
     q = recs[:, 0].astype(np.int64)

@@ -4,7 +4,8 @@ the scan's arguments passed as one struct and read again from the kernarg
 segment after its tile loop -- against sst_is_valid_peaks_device +
 sst_explain_batch_device on the same inputs, per query: status, count, the
 exact candidate bytes, every is_valid byte; a sample through the per-query
-accessor and against the CPU oracle.
+accessor; and every query against the CPU oracle: status, count, and the byte
+length and digest of its exact candidate list.
 
 Query counts sit around the scan's tile rounds: fewer tiles than waves, one
 full round of 64-query tiles over W waves, and the odd and even exits of the
@@ -14,6 +15,7 @@ workgroups' 512 / 1024 peaks."""
 import numpy as np
 import pytest
 
+import _digest
 import _oracle as oracle
 from conftest import load_golden
 from spectrseqtools_amd import _native
@@ -53,6 +55,22 @@ def dev(engine, rows):
     return t
 
 
+@pytest.fixture(scope="module")
+def orc(rows):
+    """The oracle's table and alphabet of `dev` (built once)."""
+    return oracle.build_table(rows, max(rows) * 35, 32), oracle.Alphabet(rows, *_budgets(rows))
+
+
+def check_vs_oracle(res, orc, masses, thr, mods, what):
+    """All queries of a fetched result against the oracle's digests (16 threads)."""
+    host, alph = orc
+    A = 10 if mods is None else mods
+    want = oracle.explain_digest_batch(host, 32, alph, masses, thr, A, TOL, nthreads=16)
+    one = lambda i: oracle.explain_table(host, 32, alph, masses[i], None if thr is None else thr[i], TOL,
+                                         int(np.broadcast_to(A, len(masses))[i]))[1]
+    return _digest.assert_equals_oracle(res, want, one, _native, what)
+
+
 def _queries(rng, rows, n, kind="mixed"):
     """Masses and thresholds: sums of one or two rows plus noise ("mixed":
     hits and misses on the pair list), "none": below the first reachable
@@ -89,8 +107,9 @@ def _candidate_bytes(res):
     return ln, res.payload[idx]
 
 
-def _check_step(engine, dev, masses, thr, n_peaks, rng, mods=None, expect=None):
-    """One step against the two separate calls; returns the step's result."""
+def _check_step(engine, dev, orc, masses, thr, n_peaks, rng, mods=None, expect=None):
+    """One step against the two separate calls and, every query, against the
+    oracle; returns the step's result."""
     torch = pytest.importorskip("torch")
     n = len(masses)
     dev_t = torch.device("cuda", engine.device)
@@ -122,26 +141,27 @@ def _check_step(engine, dev, masses, thr, n_peaks, rng, mods=None, expect=None):
     if expect == "all":
         assert (res.status == _native.SST_SOME).all()
     ref.close()
+    check_vs_oracle(res, orc, masses, thr, mods, f"step, n = {n}")
     return res
 
 
 @pytest.mark.parametrize("n", N_QUERIES)
-def test_step_query_counts(engine, dev, rows, n):
+def test_step_query_counts(engine, dev, orc, rows, n):
     rng = np.random.default_rng(100 + n % 97)
     masses, thr = _queries(rng, rows, n)
-    _check_step(engine, dev, masses, thr, 513, rng).close()
+    _check_step(engine, dev, orc, masses, thr, 513, rng).close()
 
 
 @pytest.mark.parametrize("n_peaks", N_PEAKS)
 @pytest.mark.parametrize("n", (65, 64 * W_STEP + 1))
-def test_step_peak_counts(engine, dev, rows, n, n_peaks):
+def test_step_peak_counts(engine, dev, orc, rows, n, n_peaks):
     rng = np.random.default_rng(200 + n_peaks)
     masses, thr = _queries(rng, rows, n)
-    _check_step(engine, dev, masses, thr, n_peaks, rng).close()
+    _check_step(engine, dev, orc, masses, thr, n_peaks, rng).close()
 
 
 @pytest.mark.parametrize("variant", ("no_thresholds", "per_query_mods", "mods_no_thresholds", "none", "all", "routed"))
-def test_step_input_variants(engine, dev, rows, variant):
+def test_step_input_variants(engine, dev, orc, rows, variant):
     rng = np.random.default_rng(300)
     n = N_VARIANT if variant != "routed" else 64 * 65 + 1  # (routed: five workgroups; the deferred DFS is slow)
     kind = variant if variant in ("none", "all", "routed") else "mixed"
@@ -149,21 +169,20 @@ def test_step_input_variants(engine, dev, rows, variant):
     mods = rng.integers(0, 12, n).astype(np.int64) if "mods" in variant else None
     if "no_thresholds" in variant:
         thr = None
-    res = _check_step(engine, dev, masses, thr, 1025, rng, mods=mods, expect=kind)
+    res = _check_step(engine, dev, orc, masses, thr, 1025, rng, mods=mods, expect=kind)
     if variant == "routed":  # windows past the pair list were answered (three and more rows)
         some = np.flatnonzero(res.status == _native.SST_SOME)
         assert (res.payload[res.offset[some].astype(np.int64)] > 2).any()  # a first candidate's row count
     res.close()
 
 
-def test_step_sample_vs_oracle(engine, dev, rows):
+def test_step_sample_vs_oracle(engine, dev, orc, rows):
     """A step's answers on a sample of its queries against the CPU oracle."""
     rng = np.random.default_rng(400)
     n = 64 * W_STEP + 65
     masses, thr = _queries(rng, rows, n)
-    res = _check_step(engine, dev, masses, thr, 513, rng)
-    host = oracle.build_table(rows, max(rows) * 35, 32)
-    alph = oracle.Alphabet(rows, *_budgets(rows))
+    res = _check_step(engine, dev, orc, masses, thr, 513, rng)
+    host, alph = orc
     for i in np.concatenate([rng.integers(0, n, 150), [0, 63, 64, n - 65, n - 64, n - 1]]):
         st, sols, n_empty, _ = oracle.explain_table(host, 32, alph, masses[i], thr[i], TOL, 10)
         want = _native.SST_OUT_OF_TABLE if st < 0 else (
