@@ -1037,6 +1037,70 @@ int sst_align_windows_device(sst_table* t, const sst_align_args* a);
  * global atomics.  Argument checks and errors as sst_align_windows_device. */
 int sst_align_split_device(sst_table* t, const sst_align_args* a);
 
+/* The certificate under the program's universal modification cap
+ * (linear_program.py:180-188: the y of rows whose name is not in
+ * UNMODIFIED_BASES sum to at most ceil(modification_rate * L)).  Everything of
+ * sst_align_windows_device's definition stays, except:
+ *   row_mod[r]  one byte per table row: 1 iff the row's first name (the name
+ *     the program's y variable carries) is not in UNMODIFIED_BASES.  This is
+ *     not the table's is_modification ("any name").
+ *   mod_cap[g]  int(ceil(modification_rate * L)) of spectrum g, computed by the
+ *     caller in f64 as the reference does; the kernels see integers only.
+ *   Position i is forced iff every row of A_i is modified; F is the number of
+ *   forced positions of the spectrum.  If F > mod_cap[g] (so also for a
+ *   negative mod_cap) no y is feasible: every fragment of the spectrum gets
+ *   SST_ALIGN_INFEASIBLE, with the precedence of an empty A_i (among modelled
+ *   spectra only).  Else the budget is E = mod_cap[g] - F >= 0.
+ *   Capped sums: S_E(l, r) = the sums of one w_a per position i in [l, r], a in
+ *   A_i, for which some choice has excess <= E, the excess of a choice being
+ *   (modified rows chosen) - (forced positions in [l, r]).  Positions outside
+ *   [l, r] cost at least their forced count and can be chosen to cost exactly
+ *   that, so S_E(l, r) is exactly what the y that satisfy the cap over the
+ *   whole sequence can place on [l, r].  Per distinct sum the smallest excess
+ *   is kept; extending by position p maps (s, e) to (s + w_a, e + row_mod[a] -
+ *   forced_p), a in A_p; excess never falls along a sweep, so an entry above E
+ *   leaves for good.  The empty interval has sum 0 and excess 0.
+ *   [l, r] is closed iff |S_E(l, r)| <= K.  Every position has a row of cost
+ *   0, so |S_E| never shrinks when an interval grows at either end, and the
+ *   set does not depend on the sweep direction.  LO / HI stay the uncapped sums
+ *   of minima / maxima: a conservative cut only (the meets test of open
+ *   intervals, the early exit); they need not be achievable under the cap.
+ *   status, n_fit, first, alignable: as defined there, with S_E for S.
+ * With row_mod all zero, or mod_cap[g] >= L, all four outputs equal
+ * sst_align_windows_device's bit for bit.  alignable here <= alignable there;
+ * an interval closed there is closed here; a FIT there may be NONE or OPEN
+ * here, a NONE there stays NONE (or INFEASIBLE).
+ * alignable == 0 stays safe by the argument above with "dropping the per-row
+ * caps (linear_program.py:190-196)" for "dropping the modification-rate
+ * constraints": those caps are not a function of one scalar per sum and stay
+ * dropped, so the certificate remains a necessary condition and alignable == 1
+ * still promises nothing.
+ * One kernel (k_align_windows_caps, sst_align_caps.hip: one u8 excess beside every
+ * u32 list entry) on the ctx stream; no scratch buffer, no global atomics.
+ * Both members of caps are device pointers.  Argument checks and errors as
+ * sst_align_windows_device, plus SST_E_ARG for a NULL caps or, with n_spec >
+ * 0, a NULL member (with a message). */
+typedef struct sst_align_caps {
+  const uint8_t* row_mod; /* [table rows] */
+  const int32_t* mod_cap; /* [n_spec] */
+} sst_align_caps;
+int sst_align_windows_caps_device(sst_table* t, const sst_align_args* a, const sst_align_caps* caps);
+
+/* The two-list split under the cap.  sst_align_split_device's definition with:
+ *   m* the largest m with S_E(l, m) closed; the second list is S_E(m* + 1, r),
+ *   its excess counted against its own forced positions; [l, r] is
+ *   split-closed while both lists are closed (by monotonicity this is again
+ *   the "exists m" rule and direction-free).  It holds a fitting sum iff some
+ *   a, b of the two lists have |a + b - target| <= W and e_a + e_b <= E (excess
+ *   adds over disjoint intervals).  Every b inside the window is tried, not
+ *   only the first one >= target - W - a.
+ * Precondition: a's four output arrays hold sst_align_windows_caps_device's
+ * result for the same a and caps; only its SST_ALIGN_OPEN fragments are
+ * recomputed, every other keeps all four outputs bit for bit, and the call is
+ * idempotent on its own output.  One kernel (k_align_split_caps) on the ctx
+ * stream.  Argument checks as sst_align_windows_caps_device. */
+int sst_align_split_caps_device(sst_table* t, const sst_align_args* a, const sst_align_caps* caps);
+
 /* compute_sequence_length_bound (mass_table.py:343-487) after the skeleton's
  * alphabet reduction (skeleton_building.py:315-336), both directions, for
  * queries on per-spectrum reduced alphabets, exact without a table rebuild:
@@ -1159,7 +1223,9 @@ int64_t sst_pyset_order(const int32_t* keys, const int64_t* hashes, int64_t n, i
 #define SST_K_TABLE_CERTIFY 20 /* k_table_certify (sst_table_certify) */
 #define SST_K_ALIGN 21 /* k_align_windows (sst_align_windows_device) */
 #define SST_K_ALIGN_SPLIT 22 /* k_align_split (sst_align_split_device) */
-#define SST_K_COUNT 24
+#define SST_K_ALIGN_CAPS 23 /* k_align_windows_caps (sst_align_windows_caps_device) */
+#define SST_K_ALIGN_SPLIT_CAPS 24 /* k_align_split_caps (sst_align_split_caps_device) */
+#define SST_K_COUNT 25
 /* When enabled, every kernel launch of this ctx is bracketed by hipEvents
  * recorded on the ctx stream; sst_profile_read synchronises and returns the
  * summed milliseconds and launch counts per kernel id since the last read

@@ -40,6 +40,7 @@ EXPORTS = (
     "sst_length_bounds_frontier_device", "sst_post_skeleton_device", "sst_ctx_trim", "sst_requery_merge_device",
     "sst_handoff_count_device", "sst_handoff_emit_device", "sst_table_scan_lds_hits", "sst_table_certify",
     "sst_align_capacity", "sst_align_windows_device", "sst_align_split_device",
+    "sst_align_windows_caps_device", "sst_align_split_caps_device",
 )
 
 # kernel ids of sst_profile_read
@@ -50,7 +51,9 @@ K_RESULT_PACK = 6
 K_TABLE_CERTIFY = 20
 K_ALIGN = 21
 K_ALIGN_SPLIT = 22
-K_COUNT = 24  # SST_K_COUNT
+K_ALIGN_CAPS = 23
+K_ALIGN_SPLIT_CAPS = 24
+K_COUNT = 25  # SST_K_COUNT
 KERNEL_NAMES = {K_IS_VALID: "k_is_valid", K_EXPLAIN_SCAN: "k_explain_scan", K_EXPLAIN_DEEP: "k_explain_deferred",
                 K_EXPLAIN_EXPAND: "k_explain_expand",
                 K_RESULT_PACK: "k_result_pack",  # ids 3, 4: reserved (merged into the deferred launch)
@@ -59,7 +62,8 @@ KERNEL_NAMES = {K_IS_VALID: "k_is_valid", K_EXPLAIN_SCAN: "k_explain_scan", K_EX
                 K_SKEL_WALK: "k_skel_walk", K_REACH_ROWS: "k_reach_rows", K_LENGTH_BOUND: "k_length_bound",
                 K_JACCARD: "k_jaccard", K_PAIRS_ALPHA: "k_pairs_alpha", K_REQUERY_MERGE: "k_requery_merge",
                 K_HANDOFF: "k_handoff", K_TABLE_CERTIFY: "k_table_certify", K_ALIGN: "k_align_windows",
-                K_ALIGN_SPLIT: "k_align_split"}
+                K_ALIGN_SPLIT: "k_align_split", K_ALIGN_CAPS: "k_align_windows_caps",
+                K_ALIGN_SPLIT_CAPS: "k_align_split_caps"}
 
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
@@ -117,6 +121,11 @@ class AlignArgs(ctypes.Structure):
                                         "frag_obs", "frag_min_end", "frag_max_end")] + \
         [("tol", ctypes.c_double), ("prec", ctypes.c_double)] + \
         [(n, ctypes.c_void_p) for n in ("status", "alignable", "n_fit", "first")]
+
+
+class AlignCaps(ctypes.Structure):
+    """sst_align_caps (include/sst.h): the universal modification cap's two device arrays."""
+    _fields_ = [("row_mod", ctypes.c_void_p), ("mod_cap", ctypes.c_void_p)]
 
 
 # sst_align_windows_device's status per fragment (SST_ALIGN_*)
@@ -345,6 +354,9 @@ def load_library(path=LIB_PATH):
     lib.sst_align_windows_device.restype = _I
     lib.sst_align_split_device.argtypes = [_P, ctypes.POINTER(AlignArgs)]
     lib.sst_align_split_device.restype = _I
+    for f in (lib.sst_align_windows_caps_device, lib.sst_align_split_caps_device):
+        f.argtypes = [_P, ctypes.POINTER(AlignArgs), ctypes.POINTER(AlignCaps)]
+        f.restype = _I
     lib.sst_jaccard_device.argtypes = [_P, ctypes.POINTER(JaccardArgs)]
     lib.sst_jaccard_device.restype = _I
     lib.sst_skeleton_alpha_device.argtypes = [_P, _I64, _P, _P, _P, _P, _P]

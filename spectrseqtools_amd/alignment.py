@@ -15,6 +15,12 @@ align_device the kernel (csrc/sst_align.hip) over a whole outcome.
 split=True (both) also decides the open intervals that cut into two closed
 halves, a fitting sum searched as a + b over the halves' sorted lists
 (sst_align_split_device); only fragments that are OPEN without it change.
+
+caps (both) carries the program's universal modification cap (linear_program
+.py:180-188) exactly: per distinct sum the fewest modified rows beyond the
+forced ones, sums that need more than the spectrum's budget leave the lists
+(sst_align_windows_caps_device, sst_align_split_caps_device; lp_caps builds the
+two inputs).  The per-row caps (:190-196) stay dropped.
 """
 import ctypes
 import math
@@ -225,7 +231,175 @@ def _align_spectrum(L, sets, row_mass, code, su, obs, mn, mx, tolerance, precisi
     return status, n_fit, np.where(n_fit > 0, first, NO_INTERVAL)
 
 
-def align_host(outcome, tolerance, precision, capacity=ALIGN_CAPACITY, split=False):
+def lp_caps(dp_table, outcome):
+    """(row_mod u8 [n_rows], mod_cap i32 [S]): the inputs of the universal cap
+    (linear_program.py:180-188).  row_mod[r] = 1 iff the row's first name (the
+    one the program's y variables carry, outcome.row_names) is not in
+    UNMODIFIED_BASES; row 0 is 0.  mod_cap[g] = int(np.ceil(modification_rate *
+    L)) in f64 as the reference computes it."""
+    from .masses import UNMODIFIED_BASES
+
+    row_mod = np.array([0] + [int(n not in UNMODIFIED_BASES) for n in outcome.row_names[1:]], dtype=np.uint8)
+    rate = float(dp_table.seq.modification_rate)
+    # (one f64 product and ceil per spectrum: the same IEEE operations as the reference's scalar ones)
+    mod_cap = np.ceil(np.float64(rate) * np.asarray(outcome.seq_len, dtype=np.float64)).astype(np.int32)
+    return row_mod, mod_cap
+
+
+def _position_costs(sets, row_mass, row_mod):
+    """Per position (distinct masses ascending, the fewest modified rows that
+    reach each: 0 / 1, forced: every row of A_i is modified)."""
+    out = []
+    for rows in sets:
+        best = {}
+        for r in rows:
+            m = int(row_mass[r])
+            best[m] = min(best.get(m, 1), int(row_mod[r] != 0))
+        masses = np.array(sorted(best), dtype=np.int64)
+        forced = int(all(best.values()))
+        out.append((masses, np.array([best[int(m)] for m in masses], dtype=np.int64) - forced, forced))
+    return out
+
+
+def _extend_capped(sums, exc, masses, cost, E):
+    """S_E extended by one position: (s + w, e + cost) for every mass, equal
+    sums keep the smallest excess, entries above E leave."""
+    s = np.add.outer(sums, masses).reshape(-1)
+    e = np.add.outer(exc, cost).reshape(-1)
+    keep = e <= E
+    s, e = s[keep], e[keep]
+    order = np.lexsort((e, s))
+    s, e = s[order], e[order]
+    head = np.concatenate([[True], s[1:] != s[:-1]]) if len(s) else np.zeros(0, bool)
+    return s[head], e[head]
+
+
+def _align_spectrum_caps(L, pc, E, code, su, obs, mn, mx, tolerance, precision, capacity, split=False):
+    """_align_spectrum under the universal cap: pc = _position_costs(...), E
+    the budget beyond the forced positions.  The lists are S_E(l, r) with the
+    smallest excess per sum; LO and HI stay the uncapped sums of minima and
+    maxima (a conservative cut only)."""
+    n = len(code)
+    status = np.zeros(n, np.uint8)
+    n_fit = np.zeros(n, np.int64)
+    first = np.full(n, 1 << 20, np.int64)
+    opened = np.zeros(n, bool)
+    cls = (code.astype(np.int64) >> 2) & 3  # 0 internal, 1 START, 2 END, 3 START_END
+    skipped = ((cls == 1) | (cls == 2)) & ((mn < 0) | (mn >= L) | (mx < 0) | (mx >= L))
+    tw = [quantise(float(s), float(o), tolerance, precision) for s, o in zip(su, obs)]
+    t = np.array([x[0] for x in tw], dtype=np.int64).reshape(n)
+    w = np.array([x[1] for x in tw], dtype=np.int64).reshape(n)
+    live = ~skipped & (w >= 0)
+    flo, fhi = t - w, t + w
+    lo_end = np.minimum(mn, mx)
+    zero = np.zeros(1, np.int64)
+
+    def fwd(l, r):
+        return internal | ((cls == 1) & (r >= lo_end) & (r <= mx)) | ((cls == 3) & (r == L - 1))
+
+    def bwd(l, r):
+        return (cls == 2) & (l >= lo_end) & (l <= mn)
+
+    def match(ok, l, r, LO, HI, sums):
+        cand = np.flatnonzero(ok & live & (fhi >= LO) & (flo <= HI))
+        if not len(cand):
+            return
+        if sums is None:
+            opened[cand] = True
+            return
+        at = np.searchsorted(sums, flo[cand], side="left")
+        fit = cand[(at < len(sums)) & (sums[np.minimum(at, len(sums) - 1)] <= fhi[cand])]
+        n_fit[fit] += 1
+        first[fit] = np.minimum(first[fit], l << 8 | r)
+
+    def sweep(start, step, ok_of):
+        sums, exc, LO, HI = zero, zero, 0, 0
+        last = int(fhi[live].max()) if live.any() else -1
+        p = start
+        while 0 <= p < L:
+            m, c, _ = pc[p]
+            LO, HI = LO + int(m[0]), HI + int(m[-1])
+            if LO > last:
+                break
+            if sums is not None:
+                sums, exc = _extend_capped(sums, exc, m, c, E)
+                if len(sums) > capacity:
+                    sums = None
+            l, r = (start, p) if step > 0 else (p, start)
+            match(ok_of(l, r), l, r, LO, HI, sums)
+            p += step
+
+    internal = cls == 0
+    if internal.any() or (L == 0 and (cls == 3).any()):
+        match(internal | ((cls == 3) & (L == 0)), 0xFF, 0xFF, 0, 0, zero)
+    for l in range(L if internal.any() else min(L, 1)):
+        sweep(l, 1, fwd if l == 0 else (lambda l, r: internal))
+    if (cls == 2).any():
+        sweep(L - 1, -1, bwd)
+
+    status[:] = np.where(skipped, ALIGN_SKIPPED, np.where(n_fit > 0, ALIGN_FIT, np.where(opened, ALIGN_OPEN, ALIGN_NONE)))
+    todo = status == ALIGN_OPEN
+    if not split or not todo.any():
+        return status, n_fit, np.where(n_fit > 0, first, NO_INTERVAL)
+
+    opened[:] = False
+    last = int(fhi[todo].max())
+
+    def split_sweep(start, step, ok_of):
+        a, ea, lo_a, hi_a = zero, zero, 0, 0  # S_E(start, m*), the last closed interval of the sweep
+        p = start
+        while 0 <= p < L:
+            m, c, _ = pc[p]
+            if lo_a + int(m[0]) > last:
+                return
+            nxt, enxt = _extend_capped(a, ea, m, c, E)
+            if len(nxt) > capacity:
+                break
+            a, ea, lo_a, hi_a = nxt, enxt, lo_a + int(m[0]), hi_a + int(m[-1])
+            p += step
+        else:
+            return
+        halves = p != start
+        b, eb, LO, HI = zero, zero, lo_a, hi_a  # S_E(m* + 1, r), its excess against its own forced positions
+        while 0 <= p < L:
+            m, c, _ = pc[p]
+            LO, HI = LO + int(m[0]), HI + int(m[-1])
+            if LO > last:
+                break
+            if halves and b is not None:
+                b, eb = _extend_capped(b, eb, m, c, E)
+                if len(b) > capacity:
+                    b = None
+            l, r = (start, p) if step > 0 else (p, start)
+            cand = np.flatnonzero(ok_of(l, r) & todo & (fhi >= LO) & (flo <= HI))
+            if not halves or b is None:
+                opened[cand] = True
+            else:
+                for j in cand:
+                    fit = False
+                    for v in np.unique(ea):  # a of excess v takes any b of excess <= E - v
+                        bb = b[eb <= E - v]
+                        if not len(bb):
+                            continue
+                        x = a[(ea == v) & (a >= flo[j] - bb[-1]) & (a <= fhi[j] - bb[0])]
+                        at = np.searchsorted(bb, flo[j] - x, side="left")
+                        if ((at < len(bb)) & (bb[np.minimum(at, len(bb) - 1)] <= fhi[j] - x)).any():
+                            fit = True
+                            break
+                    if fit:
+                        n_fit[j] += 1
+                        first[j] = min(first[j], l << 8 | r)
+            p += step
+
+    for l in range(L if (internal & todo).any() else min(L, 1)):
+        split_sweep(l, 1, fwd if l == 0 else (lambda l, r: internal))
+    if ((cls == 2) & todo).any():
+        split_sweep(L - 1, -1, bwd)
+    status[todo] = np.where(n_fit[todo] > 0, ALIGN_FIT, np.where(opened[todo], ALIGN_OPEN, ALIGN_NONE))
+    return status, n_fit, np.where(n_fit > 0, first, NO_INTERVAL)
+
+
+def align_host(outcome, tolerance, precision, capacity=ALIGN_CAPACITY, split=False, caps=None):
     """The certificate of every fragment of `outcome` (a BatchOutcome), by the
     definition: per left end the achievable sums of the growing interval as a
     sorted array, open once they number more than `capacity`.
@@ -234,7 +408,19 @@ def align_host(outcome, tolerance, precision, capacity=ALIGN_CAPACITY, split=Fal
     interval whose greedy first half and the rest are both closed holds a
     fitting sum iff some a + b of the halves' sums fits; where the rest is
     open too the interval is undecided, as every open one is without split.
-    The other fragments keep their outputs."""
+    The other fragments keep their outputs.
+    caps=(row_mod, mod_cap) (lp_caps): the universal modification cap holds
+    too (include/sst.h, sst_align_windows_caps_device).  A spectrum with more
+    forced positions (every row of A_i modified) than mod_cap[g] is
+    INFEASIBLE; else the lists are S_E(l, r), the sums some choice reaches with
+    at most E = mod_cap[g] - forced more modified rows than the interval's
+    forced positions, closed iff |S_E| <= capacity, and the split matches a + b
+    only where the two excesses together stay within E."""
+    if caps is not None:
+        row_mod = np.ascontiguousarray(caps[0], dtype=np.uint8)
+        mod_cap = np.ascontiguousarray(caps[1], dtype=np.int32)
+        if len(row_mod) != len(outcome.row_mass) or len(mod_cap) != len(outcome):
+            raise ValueError("align_host: caps do not match the outcome's rows / spectra")
     S, nf = len(outcome), int(outcome.frag_off[-1])
     status = np.zeros(nf, np.uint8)
     n_fit = np.zeros(nf, np.uint32)
@@ -255,6 +441,19 @@ def align_host(outcome, tolerance, precision, capacity=ALIGN_CAPACITY, split=Fal
         if any(not rows for rows in sets):
             status[f] = ALIGN_INFEASIBLE
             continue
+        if caps is not None:
+            pc = _position_costs(sets, outcome.row_mass, row_mod)
+            forced = sum(x[2] for x in pc)
+            if forced > int(mod_cap[g]):
+                status[f] = ALIGN_INFEASIBLE
+                continue
+            st, nn, ff = _align_spectrum_caps(L, pc, min(int(mod_cap[g]) - forced, L), outcome.frag_code[f],
+                                              outcome.frag_su[f], outcome.frag_obs[f],
+                                              outcome.frag_min_end[f].astype(np.int64),
+                                              outcome.frag_max_end[f].astype(np.int64), tolerance, precision,
+                                              int(capacity), split)
+            status[f], n_fit[f], first[f] = st, nn, ff
+            continue
         st, nn, ff = _align_spectrum(L, sets, outcome.row_mass, outcome.frag_code[f], outcome.frag_su[f],
                                      outcome.frag_obs[f], outcome.frag_min_end[f].astype(np.int64),
                                      outcome.frag_max_end[f].astype(np.int64), tolerance, precision, int(capacity),
@@ -264,21 +463,31 @@ def align_host(outcome, tolerance, precision, capacity=ALIGN_CAPACITY, split=Fal
     return AlignOutcome(frag_off=outcome.frag_off.copy(), status=status, alignable=alignable, n_fit=n_fit, first=first)
 
 
-def align_device(dp_table, outcome, split=False):
+def align_device(dp_table, outcome, split=False, caps=False):
     """The certificate of every fragment of `outcome` on dp_table's device
     (sst_align_windows_device, capacity sst_align_capacity()): one upload per
     input array, one launch, one download per output array.  `outcome` must be
     on dp_table's rows.  split=True: sst_align_split_device follows on the
-    same stream before the one download (align_host's split=True)."""
+    same stream before the one download (align_host's split=True).
+    caps=True: the universal modification cap holds too (lp_caps(dp_table,
+    outcome) uploaded, sst_align_windows_caps_device and, with split,
+    sst_align_split_caps_device: align_host's caps=lp_caps(...)); a (row_mod,
+    mod_cap) pair is taken as it is."""
     from .pipeline_device import _one_stream
 
     masses = [int(m.mass) for m in dp_table.masses]
     if masses != [int(x) for x in outcome.row_mass]:
         raise ValueError("align_device: the outcome is not on this table's rows")
-    return _one_stream(_align_device)(dp_table, outcome, split)
+    if caps is True:
+        caps = lp_caps(dp_table, outcome)
+    elif caps is False:
+        caps = None
+    if caps is not None and (len(caps[0]) != len(masses) or len(caps[1]) != len(outcome)):
+        raise ValueError("align_device: caps do not match the table's rows / the outcome's spectra")
+    return _one_stream(_align_device)(dp_table, outcome, split, caps)
 
 
-def _align_device(dp_table, o, split=False):
+def _align_device(dp_table, o, split=False, caps=None):
     import torch
 
     dt = dp_table.device_table
@@ -307,10 +516,20 @@ def _align_device(dp_table, o, split=False):
      a.frag_max_end) = (x.data_ptr() for x in keep)
     a.tol, a.prec = float(dp_table.tolerance), float(dp_table.precision)
     a.status, a.alignable, a.n_fit, a.first = (x.data_ptr() for x in (status, alignable, n_fit, first))
+    if caps is not None:
+        keep += [up(caps[0], np.uint8), up(caps[1], np.int32)]
+        c = _native.AlignCaps(keep[-2].data_ptr(), keep[-1].data_ptr())
     torch.cuda.synchronize(dev)
-    eng.check(eng._lib.sst_align_windows_device(dt.handle, ctypes.byref(a)), "sst_align_windows_device")
-    if split:
-        eng.check(eng._lib.sst_align_split_device(dt.handle, ctypes.byref(a)), "sst_align_split_device")
+    if caps is None:
+        eng.check(eng._lib.sst_align_windows_device(dt.handle, ctypes.byref(a)), "sst_align_windows_device")
+        if split:
+            eng.check(eng._lib.sst_align_split_device(dt.handle, ctypes.byref(a)), "sst_align_split_device")
+    else:
+        eng.check(eng._lib.sst_align_windows_caps_device(dt.handle, ctypes.byref(a), ctypes.byref(c)),
+                  "sst_align_windows_caps_device")
+        if split:
+            eng.check(eng._lib.sst_align_split_caps_device(dt.handle, ctypes.byref(a), ctypes.byref(c)),
+                      "sst_align_split_caps_device")
     eng.synchronize()
     return AlignOutcome(frag_off=o.frag_off.copy(), status=status.cpu().numpy(), alignable=alignable.cpu().numpy(),
                         n_fit=n_fit.cpu().numpy().view(np.uint32), first=first.cpu().numpy().view(np.uint16))

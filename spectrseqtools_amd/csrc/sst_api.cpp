@@ -3783,6 +3783,35 @@ extern "C" int sst_align_split_device(sst_table* t, const sst_align_args* a) {
   return SST_OK;
 }
 
+// align_args_check, and the caps' two members
+static int align_caps_check(sst_table* t, const sst_align_args* a, const sst_align_caps* caps, const char* who) {
+  if (!caps) return SST_E_ARG;
+  const int rc = align_args_check(t, a);
+  if (rc == 1 && (!caps->row_mod || !caps->mod_cap))
+    return fail(t->ctx, SST_E_ARG, std::string(who) + ": a NULL member of sst_align_caps");
+  return rc;
+}
+
+extern "C" int sst_align_windows_caps_device(sst_table* t, const sst_align_args* a, const sst_align_caps* caps) {
+  if (int rc = align_caps_check(t, a, caps, "sst_align_windows_caps_device"); rc != 1) return rc;
+  sst_ctx* c = t->ctx;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  if (int rc = set_device(c)) return rc;
+  Prof p(c, SST_K_ALIGN_CAPS);
+  HIP_OK(c, sst::launch_align_windows_caps(*a, *caps, t->args.w, t->n_rows, 2 * c->n_cu, c->stream));
+  return SST_OK;
+}
+
+extern "C" int sst_align_split_caps_device(sst_table* t, const sst_align_args* a, const sst_align_caps* caps) {
+  if (int rc = align_caps_check(t, a, caps, "sst_align_split_caps_device"); rc != 1) return rc;
+  sst_ctx* c = t->ctx;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  if (int rc = set_device(c)) return rc;
+  Prof p(c, SST_K_ALIGN_SPLIT_CAPS);
+  HIP_OK(c, sst::launch_align_split_caps(*a, *caps, t->args.w, t->n_rows, 2 * c->n_cu, c->stream));
+  return SST_OK;
+}
+
 extern "C" int sst_skeleton_alpha_device(sst_table* t, int64_t n_spec, const int32_t* d_max_len,
                                          const uint64_t* d_skel_off, const uint64_t* d_skel, const uint64_t* d_alpha,
                                          uint64_t* d_out) {

@@ -50,7 +50,7 @@ GPU-busy share of its wall time.
 
 Usage: python tools/pipeline_bench.py [--spectra 100000] [--seed 7] [--host-driven]
        [--backend nccl|gloo] [--dump-outcomes DIR] [--as-rank R] [--handoff [--handoff-repeats 3]]
-       [--align | --align-split]
+       [--align | --align-split] [--align-caps] [--modification-rate 0.5]
 """
 import argparse
 import json
@@ -299,7 +299,7 @@ def unconstrained_runs(out, spectra, free=None):
     return np.array(longest, dtype=np.int64), np.array(count, dtype=np.int64)
 
 
-def align_stage(pd, dp, rows, ln, post, kernels, split=False):
+def align_stage(pd, dp, rows, ln, post, kernels, split=False, caps=False):
     """--align: the alignment certificate (alignment.align_device) over the
     hand-off of the spectra the stages ran -- wall seconds from the host
     arrays in to the host arrays out (uploads, k_align_windows, downloads), the
@@ -309,7 +309,13 @@ def align_stage(pd, dp, rows, ln, post, kernels, split=False):
     (k_align_split follows k_align_windows on the stream, one download); the
     base certificate is then taken again, untimed, for the shares before the
     split, what became of the base-OPEN fragments, and what the spectra that
-    are still OPEN look like."""
+    are still OPEN look like.
+    --align-caps (caps=True): the timed call runs under the universal
+    modification cap (align_device(caps=True): k_align_windows_caps and, with
+    --align-split, k_align_split_caps); the split's base is then the caps base.
+    The uncapped certificate of the same run (same split) is taken again,
+    untimed, for its shares, the fragments the cap moved, the spectra it makes
+    INFEASIBLE and the mod_cap distribution ("caps")."""
     from spectrseqtools_amd import _native, alignment
 
     S = len(ln.seq_len)
@@ -324,7 +330,7 @@ def align_stage(pd, dp, rows, ln, post, kernels, split=False):
                           breakage_names=rows.names, row_names=empty.row_names, row_mass=empty.row_mass)
     kernels()  # (the hand-off's launches are not this stage's)
     t0 = time.perf_counter()
-    al = alignment.align_device(dp, out, split=split)
+    al = alignment.align_device(dp, out, split=split, caps=caps)
     s = time.perf_counter() - t0
     kern = kernels()
     n = np.diff(out.frag_off)
@@ -335,9 +341,31 @@ def align_stage(pd, dp, rows, ln, post, kernels, split=False):
            "status_shares": al.shares(), "not_alignable_share": float(1.0 - al.alignable.mean()) if len(al.status) else 0.0,
            "not_alignable_share_internal": float(1.0 - al.alignable[internal].mean()) if internal.any() else 0.0,
            "path": "device (sst_align_windows_device), host arrays in and out", "kernels": kern}
+    if caps:
+        rec["path"] = "device (sst_align_windows_caps_device), host arrays in and out"
+        plain = alignment.align_device(dp, out, split=split)  # untimed: the same run without the cap
+        kernels()
+        st = _native
+        was = lambda a, b: int(((plain.status == a) & (al.status == b)).sum())  # noqa: E731
+        by_cap = (plain.status != st.ALIGN_INFEASIBLE) & (al.status == st.ALIGN_INFEASIBLE)
+        mod_cap = alignment.lp_caps(dp, out)[1][act]
+        rec["caps"] = {"modification_rate": float(dp.seq.modification_rate),
+                       "status_shares_uncapped": plain.shares(),
+                       "not_alignable_share_uncapped": float(1.0 - plain.alignable.mean()) if len(plain.status) else 0.0,
+                       "solver_calls_saved_by_the_cap": int((plain.alignable != 0).sum() - (al.alignable != 0).sum()),
+                       "alignable_never_raised": bool((al.alignable <= plain.alignable).all()),
+                       "fit_to_none": was(st.ALIGN_FIT, st.ALIGN_NONE), "fit_to_open": was(st.ALIGN_FIT, st.ALIGN_OPEN),
+                       "open_to_fit": was(st.ALIGN_OPEN, st.ALIGN_FIT), "open_to_none": was(st.ALIGN_OPEN, st.ALIGN_NONE),
+                       "open_uncapped": int((plain.status == st.ALIGN_OPEN).sum()),
+                       "open_capped": int((al.status == st.ALIGN_OPEN).sum()),
+                       "fragments_infeasible_by_cap": int(by_cap.sum()),
+                       "spectra_infeasible_by_cap": int(len(np.unique(np.repeat(np.arange(S), np.diff(out.frag_off))[by_cap]))),
+                       "mod_cap_counts": {str(int(v)): int(c) for v, c in zip(*np.unique(mod_cap, return_counts=True))},
+                       "kernel_ms": {str(k): kern.get(_native.KERNEL_NAMES[k], (0.0, 0))[0]
+                                     for k in (_native.K_ALIGN_CAPS, _native.K_ALIGN_SPLIT_CAPS)}}
     if not split:
         return rec
-    base = alignment.align_device(dp, out)  # untimed: what the split started from
+    base = alignment.align_device(dp, out, caps=caps)  # untimed: what the split started from
     kernels()
     was_open = base.status == _native.ALIGN_OPEN
     still = al.status == _native.ALIGN_OPEN
@@ -362,7 +390,8 @@ def align_stage(pd, dp, rows, ln, post, kernels, split=False):
                 "log2_combinations": pct([float(np.log2(np.maximum(x, 1)).sum()) for x in per])}
 
     unchanged = all(np.array_equal(getattr(al, k)[~was_open], getattr(base, k)[~was_open]) for k in al.FRAGMENT_FIELDS)
-    rec.update({"path": "device (sst_align_windows_device + sst_align_split_device), host arrays in and out",
+    rec.update({"path": "device (sst_align_windows_caps_device + sst_align_split_caps_device), host arrays in and out"
+                if caps else "device (sst_align_windows_device + sst_align_split_device), host arrays in and out",
                 "status_shares_base": base.shares(),
                 "open_decided_share": float((was_open & ~still).sum()) / n_open,
                 "open_to_fit_share": float((was_open & (al.status == _native.ALIGN_FIT)).sum()) / n_open,
@@ -371,7 +400,8 @@ def align_stage(pd, dp, rows, ln, post, kernels, split=False):
                 "not_alignable_share_base": float(1.0 - base.alignable.mean()) if len(base.status) else 0.0,
                 "other_fragments_unchanged": bool(unchanged),
                 "kernel_ms": {str(k): kern.get(_native.KERNEL_NAMES[k], (0.0, 0))[0]
-                              for k in (_native.K_ALIGN, _native.K_ALIGN_SPLIT)},
+                              for k in ((_native.K_ALIGN_CAPS, _native.K_ALIGN_SPLIT_CAPS) if caps else
+                                        (_native.K_ALIGN, _native.K_ALIGN_SPLIT))},
                 "split_spectra": describe(was_open),  # the spectra k_align_split swept (a base-OPEN fragment)
                 "open_after_split": describe(still)})
     return rec
@@ -418,10 +448,18 @@ def main():
                          "stage also reports the shares before the split, the share of the base-OPEN fragments it "
                          "decides (open_decided_share) and turns into NONE (open_to_none_share), each kernel's "
                          "milliseconds, and what the spectra that stay OPEN look like")
+    ap.add_argument("--align-caps", action="store_true",
+                    help="--align under the program's universal modification cap (align_device(caps=True)); alone or "
+                         "with --align-split.  The stage also reports the uncapped shares of the same run (untimed), "
+                         "the fragments the cap moved (FIT -> NONE, OPEN -> FIT, OPEN -> NONE), the spectra it makes "
+                         "INFEASIBLE and the mod_cap distribution")
+    ap.add_argument("--modification-rate", type=float, default=0.5,
+                    help="the sequences' universal modification rate: the synthetic spectra's and the table's "
+                         "SequenceInformation's (0.05: the low-modification-rate variant)")
     ap.add_argument("--as-rank", type=int, default=None,
                     help="single process: generate the spectra rank R of a multi-rank run would get")
     args = ap.parse_args()
-    args.align = args.align or args.align_split
+    args.align = args.align or args.align_split or args.align_caps
 
     import torch
 
@@ -458,13 +496,13 @@ def main():
     comm_dev = torch.device("cuda", gpu) if args.backend == "nccl" else torch.device("cpu")
     t0 = time.perf_counter()
     data_rank = rank if args.as_rank is None else args.as_rank
-    batch = make_spectra(args.spectra, seed=args.seed + 1_000_003 * data_rank)
+    batch = make_spectra(args.spectra, seed=args.seed + 1_000_003 * data_rank, mod_rate=args.modification_rate)
     gen_s = time.perf_counter() - t0
     bd = build_breakage_dict(555.1294, 455.1491)
     w_full = [k for k, v in bd.items() if "START_END" in v][0]
     su_seq = batch.seq_mass - w_full * TOLERANCE  # cli.py:149-156
     seq0 = SequenceInformation(max_len=20, su_mass=float(su_seq[0]), obs_mass=float(batch.seq_mass[0]),
-                               modification_rate=0.5)
+                               modification_rate=args.modification_rate)
     dp = DynamicProgrammingTable(EXPLANATION_MASSES, compression_rate=32, tolerance=MATCHING_THRESHOLD,
                                  precision=TOLERANCE, seq=seq0, engine=engine)
     min_int = min(m.mass for m in dp.masses[1:])
@@ -515,7 +553,7 @@ def main():
         lw = pd.length_device(dp, kw, bw.alpha_dev, su_seq[:S0], batch.seq_mass[:S0], trim=False)
         pw = pd.post_skeleton_device(dp, rw, kw, lw)
         if args.align:
-            align_stage(pd, dp, rw, lw, pw, lambda: {}, split=args.align_split)
+            align_stage(pd, dp, rw, lw, pw, lambda: {}, split=args.align_split, caps=args.align_caps)
         # the reach buffer at length_device's batch budget, as a serving
         # process holds it: the timed stage allocates nothing (its hipMalloc /
         # hipFree of tens of GB took 0.1-3 s from run to run)
@@ -683,7 +721,7 @@ def main():
                                     + (f" ({'RCCL' if args.backend == 'nccl' else 'gloo'})" if dist else " (local)")}
     if rows is not None and args.align:
         barrier()
-        stages["align"] = align_stage(pd, dp, rows, ln, post, kernels, split=args.align_split)
+        stages["align"] = align_stage(pd, dp, rows, ln, post, kernels, split=args.align_split, caps=args.align_caps)
         stages["align"]["s"] = tmax(stages["align"]["s"])
         busy(stages["align"])
         progress("align")
