@@ -1075,7 +1075,7 @@ int sst_align_split_device(sst_table* t, const sst_align_args* a);
  * constraints": those caps are not a function of one scalar per sum and stay
  * dropped, so the certificate remains a necessary condition and alignable == 1
  * still promises nothing.
- * One kernel (k_align_windows_caps, sst_align_caps.hip: one u8 excess beside every
+ * One kernel (k_align_windows_caps, sst_align.hip: one u8 excess beside every
  * u32 list entry) on the ctx stream; no scratch buffer, no global atomics.
  * Both members of caps are device pointers.  Argument checks and errors as
  * sst_align_windows_device, plus SST_E_ARG for a NULL caps or, with n_spec >

@@ -116,121 +116,6 @@ def position_sets(skeleton, alpha, n_rows):
     return out
 
 
-def _align_spectrum(L, sets, row_mass, code, su, obs, mn, mx, tolerance, precision, capacity, split=False):
-    n = len(code)
-    status = np.zeros(n, np.uint8)
-    n_fit = np.zeros(n, np.int64)
-    first = np.full(n, 1 << 20, np.int64)
-    opened = np.zeros(n, bool)
-    cls = (code.astype(np.int64) >> 2) & 3  # 0 internal, 1 START, 2 END, 3 START_END
-    skipped = ((cls == 1) | (cls == 2)) & ((mn < 0) | (mn >= L) | (mx < 0) | (mx >= L))
-    tw = [quantise(float(s), float(o), tolerance, precision) for s, o in zip(su, obs)]
-    t = np.array([x[0] for x in tw], dtype=np.int64).reshape(n)
-    w = np.array([x[1] for x in tw], dtype=np.int64).reshape(n)
-    live = ~skipped & (w >= 0)
-    flo, fhi = t - w, t + w
-    lo_end = np.minimum(mn, mx)
-    masses = [np.array(sorted({int(row_mass[r]) for r in rows}), dtype=np.int64) for rows in sets]
-
-    def match(ok, l, r, LO, HI, sums):
-        """Fragments `ok` against interval (l, r): sums None for an open one."""
-        cand = np.flatnonzero(ok & live & (fhi >= LO) & (flo <= HI))
-        if not len(cand):
-            return
-        if sums is None:
-            opened[cand] = True
-            return
-        at = np.searchsorted(sums, flo[cand], side="left")
-        fit = cand[(at < len(sums)) & (sums[np.minimum(at, len(sums) - 1)] <= fhi[cand])]
-        n_fit[fit] += 1
-        first[fit] = np.minimum(first[fit], l << 8 | r)
-
-    def sweep(start, step, ok_of):
-        sums, LO, HI = np.zeros(1, np.int64), 0, 0
-        last = int(fhi[live].max()) if live.any() else -1
-        p = start
-        while 0 <= p < L:
-            m = masses[p]
-            LO, HI = LO + int(m[0]), HI + int(m[-1])
-            if LO > last:  # masses are >= 0: LO never falls
-                break
-            if sums is not None:
-                sums = np.unique(np.add.outer(sums, m)) if len(m) > 1 else sums + m[0]
-                if len(sums) > capacity:
-                    sums = None
-            l, r = (start, p) if step > 0 else (p, start)
-            match(ok_of(l, r), l, r, LO, HI, sums)
-            p += step
-
-    internal = cls == 0
-    if internal.any() or (L == 0 and (cls == 3).any()):
-        match(internal | ((cls == 3) & (L == 0)), 0xFF, 0xFF, 0, 0, np.zeros(1, np.int64))
-    for l in range(L if internal.any() else min(L, 1)):
-        if l == 0:
-            sweep(0, 1, lambda l, r: internal | ((cls == 1) & (r >= lo_end) & (r <= mx)) | ((cls == 3) & (r == L - 1)))
-        else:
-            sweep(l, 1, lambda l, r: internal)
-    if (cls == 2).any():
-        sweep(L - 1, -1, lambda l, r: (cls == 2) & (l >= lo_end) & (l <= mn))
-
-    status[:] = np.where(skipped, ALIGN_SKIPPED, np.where(n_fit > 0, ALIGN_FIT, np.where(opened, ALIGN_OPEN, ALIGN_NONE)))
-    todo = status == ALIGN_OPEN
-    if not split or not todo.any():
-        return status, n_fit, np.where(n_fit > 0, first, NO_INTERVAL)
-
-    # the split: the base-OPEN fragments again, over the open intervals only
-    opened[:] = False
-    last = int(fhi[todo].max())
-
-    def split_sweep(start, step, ok_of):
-        a, lo_a, hi_a = np.zeros(1, np.int64), 0, 0  # S(start, m*), the last closed interval of the sweep
-        p = start
-        while 0 <= p < L:
-            m = masses[p]
-            if lo_a + int(m[0]) > last:
-                return
-            nxt = np.unique(np.add.outer(a, m)) if len(m) > 1 else a + m[0]
-            if len(nxt) > capacity:
-                break
-            a, lo_a, hi_a = nxt, lo_a + int(m[0]), hi_a + int(m[-1])
-            p += step
-        else:
-            return  # every interval of the sweep is closed
-        halves = p != start  # (else not even one position is closed: nothing splits)
-        b, LO, HI = np.zeros(1, np.int64), lo_a, hi_a
-        while 0 <= p < L:
-            m = masses[p]
-            LO, HI = LO + int(m[0]), HI + int(m[-1])
-            if LO > last:
-                break
-            if halves and b is not None:
-                b = np.unique(np.add.outer(b, m)) if len(m) > 1 else b + m[0]
-                if len(b) > capacity:
-                    b = None  # undecided from here on
-            l, r = (start, p) if step > 0 else (p, start)
-            cand = np.flatnonzero(ok_of(l, r) & todo & (fhi >= LO) & (flo <= HI))
-            if not halves or b is None:
-                opened[cand] = True
-            else:
-                for j in cand:
-                    x = a[(a >= flo[j] - b[-1]) & (a <= fhi[j] - b[0])]
-                    at = np.searchsorted(b, flo[j] - x, side="left")
-                    if ((at < len(b)) & (b[np.minimum(at, len(b) - 1)] <= fhi[j] - x)).any():
-                        n_fit[j] += 1
-                        first[j] = min(first[j], l << 8 | r)
-            p += step
-
-    for l in range(L if (internal & todo).any() else min(L, 1)):
-        if l == 0:
-            split_sweep(0, 1, lambda l, r: internal | ((cls == 1) & (r >= lo_end) & (r <= mx)) | ((cls == 3) & (r == L - 1)))
-        else:
-            split_sweep(l, 1, lambda l, r: internal)
-    if ((cls == 2) & todo).any():
-        split_sweep(L - 1, -1, lambda l, r: (cls == 2) & (l >= lo_end) & (l <= mn))
-    status[todo] = np.where(n_fit[todo] > 0, ALIGN_FIT, np.where(opened[todo], ALIGN_OPEN, ALIGN_NONE))
-    return status, n_fit, np.where(n_fit > 0, first, NO_INTERVAL)
-
-
 def lp_caps(dp_table, outcome):
     """(row_mod u8 [n_rows], mod_cap i32 [S]): the inputs of the universal cap
     (linear_program.py:180-188).  row_mod[r] = 1 iff the row's first name (the
@@ -246,11 +131,16 @@ def lp_caps(dp_table, outcome):
     return row_mod, mod_cap
 
 
-def _position_costs(sets, row_mass, row_mod):
+def _position_costs(sets, row_mass, row_mod=None):
     """Per position (distinct masses ascending, the fewest modified rows that
-    reach each: 0 / 1, forced: every row of A_i is modified)."""
+    reach each: 0 / 1, forced: every row of A_i is modified).  Without row_mod
+    (no cap) no row counts as modified: every cost is 0 and nothing is forced."""
     out = []
     for rows in sets:
+        if row_mod is None:
+            masses = np.array(sorted({int(row_mass[r]) for r in rows}), dtype=np.int64)
+            out.append((masses, np.zeros(len(masses), np.int64), 0))
+            continue
         best = {}
         for r in rows:
             m = int(row_mass[r])
@@ -264,6 +154,11 @@ def _position_costs(sets, row_mass, row_mod):
 def _extend_capped(sums, exc, masses, cost, E):
     """S_E extended by one position: (s + w, e + cost) for every mass, equal
     sums keep the smallest excess, entries above E leave."""
+    if len(masses) == 1:  # one mass costs nothing (forced, or an unmodified row has it): only the sums move
+        return sums + masses[0], exc
+    if not cost.any() and not exc.any():  # nothing paid so far, nothing to pay here (always so without the cap)
+        s = np.unique(np.add.outer(sums, masses))
+        return s, np.zeros(len(s), np.int64)
     s = np.add.outer(sums, masses).reshape(-1)
     e = np.add.outer(exc, cost).reshape(-1)
     keep = e <= E
@@ -274,9 +169,10 @@ def _extend_capped(sums, exc, masses, cost, E):
     return s[head], e[head]
 
 
-def _align_spectrum_caps(L, pc, E, code, su, obs, mn, mx, tolerance, precision, capacity, split=False):
-    """_align_spectrum under the universal cap: pc = _position_costs(...), E
-    the budget beyond the forced positions.  The lists are S_E(l, r) with the
+def _align_spectrum(L, pc, E, code, su, obs, mn, mx, tolerance, precision, capacity, split=False):
+    """The certificate of one modelled spectrum: pc = _position_costs(...), E
+    the budget beyond the forced positions (without the cap: costs all 0 and
+    E = L, so nothing ever leaves a list).  The lists are S_E(l, r) with the
     smallest excess per sum; LO and HI stay the uncapped sums of minima and
     maxima (a conservative cut only)."""
     n = len(code)
@@ -301,6 +197,7 @@ def _align_spectrum_caps(L, pc, E, code, su, obs, mn, mx, tolerance, precision, 
         return (cls == 2) & (l >= lo_end) & (l <= mn)
 
     def match(ok, l, r, LO, HI, sums):
+        """Fragments `ok` against interval (l, r): sums None for an open one."""
         cand = np.flatnonzero(ok & live & (fhi >= LO) & (flo <= HI))
         if not len(cand):
             return
@@ -342,6 +239,7 @@ def _align_spectrum_caps(L, pc, E, code, su, obs, mn, mx, tolerance, precision, 
     if not split or not todo.any():
         return status, n_fit, np.where(n_fit > 0, first, NO_INTERVAL)
 
+    # the split: the base-OPEN fragments again, over the open intervals only
     opened[:] = False
     last = int(fhi[todo].max())
 
@@ -358,8 +256,8 @@ def _align_spectrum_caps(L, pc, E, code, su, obs, mn, mx, tolerance, precision, 
             a, ea, lo_a, hi_a = nxt, enxt, lo_a + int(m[0]), hi_a + int(m[-1])
             p += step
         else:
-            return
-        halves = p != start
+            return  # every interval of the sweep is closed
+        halves = p != start  # (else not even one position is closed: nothing splits)
         b, eb, LO, HI = zero, zero, lo_a, hi_a  # S_E(m* + 1, r), its excess against its own forced positions
         while 0 <= p < L:
             m, c, _ = pc[p]
@@ -369,26 +267,24 @@ def _align_spectrum_caps(L, pc, E, code, su, obs, mn, mx, tolerance, precision, 
             if halves and b is not None:
                 b, eb = _extend_capped(b, eb, m, c, E)
                 if len(b) > capacity:
-                    b = None
+                    b = None  # undecided from here on
             l, r = (start, p) if step > 0 else (p, start)
             cand = np.flatnonzero(ok_of(l, r) & todo & (fhi >= LO) & (flo <= HI))
             if not halves or b is None:
                 opened[cand] = True
-            else:
+            elif len(cand):
+                # a of excess v takes any b of excess <= E - v
+                pairs = [(a[ea == v], b[eb <= E - v]) for v in (np.unique(ea) if ea.any() else (0,))]
                 for j in cand:
-                    fit = False
-                    for v in np.unique(ea):  # a of excess v takes any b of excess <= E - v
-                        bb = b[eb <= E - v]
+                    for aa, bb in pairs:
                         if not len(bb):
                             continue
-                        x = a[(ea == v) & (a >= flo[j] - bb[-1]) & (a <= fhi[j] - bb[0])]
+                        x = aa[(aa >= flo[j] - bb[-1]) & (aa <= fhi[j] - bb[0])]
                         at = np.searchsorted(bb, flo[j] - x, side="left")
                         if ((at < len(bb)) & (bb[np.minimum(at, len(bb) - 1)] <= fhi[j] - x)).any():
-                            fit = True
+                            n_fit[j] += 1
+                            first[j] = min(first[j], l << 8 | r)
                             break
-                    if fit:
-                        n_fit[j] += 1
-                        first[j] = min(first[j], l << 8 | r)
             p += step
 
     for l in range(L if (internal & todo).any() else min(L, 1)):
@@ -416,6 +312,7 @@ def align_host(outcome, tolerance, precision, capacity=ALIGN_CAPACITY, split=Fal
     at most E = mod_cap[g] - forced more modified rows than the interval's
     forced positions, closed iff |S_E| <= capacity, and the split matches a + b
     only where the two excesses together stay within E."""
+    row_mod = None
     if caps is not None:
         row_mod = np.ascontiguousarray(caps[0], dtype=np.uint8)
         mod_cap = np.ascontiguousarray(caps[1], dtype=np.int32)
@@ -441,20 +338,13 @@ def align_host(outcome, tolerance, precision, capacity=ALIGN_CAPACITY, split=Fal
         if any(not rows for rows in sets):
             status[f] = ALIGN_INFEASIBLE
             continue
-        if caps is not None:
-            pc = _position_costs(sets, outcome.row_mass, row_mod)
-            forced = sum(x[2] for x in pc)
-            if forced > int(mod_cap[g]):
-                status[f] = ALIGN_INFEASIBLE
-                continue
-            st, nn, ff = _align_spectrum_caps(L, pc, min(int(mod_cap[g]) - forced, L), outcome.frag_code[f],
-                                              outcome.frag_su[f], outcome.frag_obs[f],
-                                              outcome.frag_min_end[f].astype(np.int64),
-                                              outcome.frag_max_end[f].astype(np.int64), tolerance, precision,
-                                              int(capacity), split)
-            status[f], n_fit[f], first[f] = st, nn, ff
+        pc = _position_costs(sets, outcome.row_mass, row_mod)
+        forced = sum(x[2] for x in pc)
+        cap = L if caps is None else int(mod_cap[g])  # (no cap: nothing is forced and E = L)
+        if forced > cap:
+            status[f] = ALIGN_INFEASIBLE
             continue
-        st, nn, ff = _align_spectrum(L, sets, outcome.row_mass, outcome.frag_code[f], outcome.frag_su[f],
+        st, nn, ff = _align_spectrum(L, pc, min(cap - forced, L), outcome.frag_code[f], outcome.frag_su[f],
                                      outcome.frag_obs[f], outcome.frag_min_end[f].astype(np.int64),
                                      outcome.frag_max_end[f].astype(np.int64), tolerance, precision, int(capacity),
                                      split)
@@ -487,6 +377,11 @@ def align_device(dp_table, outcome, split=False, caps=False):
     return _one_stream(_align_device)(dp_table, outcome, split, caps)
 
 
+# (the certificate, then its split) by "under the cap"
+_ENTRY_POINTS = {False: ("sst_align_windows_device", "sst_align_split_device"),
+                 True: ("sst_align_windows_caps_device", "sst_align_split_caps_device")}
+
+
 def _align_device(dp_table, o, split=False, caps=None):
     import torch
 
@@ -516,20 +411,13 @@ def _align_device(dp_table, o, split=False, caps=None):
      a.frag_max_end) = (x.data_ptr() for x in keep)
     a.tol, a.prec = float(dp_table.tolerance), float(dp_table.precision)
     a.status, a.alignable, a.n_fit, a.first = (x.data_ptr() for x in (status, alignable, n_fit, first))
+    extra = ()
     if caps is not None:
         keep += [up(caps[0], np.uint8), up(caps[1], np.int32)]
-        c = _native.AlignCaps(keep[-2].data_ptr(), keep[-1].data_ptr())
+        extra = (ctypes.byref(_native.AlignCaps(keep[-2].data_ptr(), keep[-1].data_ptr())),)
     torch.cuda.synchronize(dev)
-    if caps is None:
-        eng.check(eng._lib.sst_align_windows_device(dt.handle, ctypes.byref(a)), "sst_align_windows_device")
-        if split:
-            eng.check(eng._lib.sst_align_split_device(dt.handle, ctypes.byref(a)), "sst_align_split_device")
-    else:
-        eng.check(eng._lib.sst_align_windows_caps_device(dt.handle, ctypes.byref(a), ctypes.byref(c)),
-                  "sst_align_windows_caps_device")
-        if split:
-            eng.check(eng._lib.sst_align_split_caps_device(dt.handle, ctypes.byref(a), ctypes.byref(c)),
-                      "sst_align_split_caps_device")
+    for name in _ENTRY_POINTS[caps is not None][:2 if split else 1]:
+        eng.check(getattr(eng._lib, name)(dt.handle, ctypes.byref(a), *extra), name)
     eng.synchronize()
     return AlignOutcome(frag_off=o.frag_off.copy(), status=status.cpu().numpy(), alignable=alignable.cpu().numpy(),
                         n_fit=n_fit.cpu().numpy().view(np.uint32), first=first.cpu().numpy().view(np.uint16))

@@ -3763,23 +3763,14 @@ static int align_args_check(const sst_table* t, const sst_align_args* a) {
   return 1;
 }
 
-extern "C" int sst_align_windows_device(sst_table* t, const sst_align_args* a) {
-  if (int rc = align_args_check(t, a); rc != 1) return rc;
+// Both checks passed (rc == 1): the launch of one of the four kernels under its profile id; else rc.
+static int align_launch(int rc, sst_table* t, const sst_align_args* a, const sst_align_caps* caps, int kid, bool split) {
+  if (rc != 1) return rc;
   sst_ctx* c = t->ctx;
   std::lock_guard<std::recursive_mutex> g(c->mu);
-  if (int rc = set_device(c)) return rc;
-  Prof p(c, SST_K_ALIGN);
-  HIP_OK(c, sst::launch_align_windows(*a, t->args.w, t->n_rows, 2 * c->n_cu, c->stream));
-  return SST_OK;
-}
-
-extern "C" int sst_align_split_device(sst_table* t, const sst_align_args* a) {
-  if (int rc = align_args_check(t, a); rc != 1) return rc;
-  sst_ctx* c = t->ctx;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  if (int rc = set_device(c)) return rc;
-  Prof p(c, SST_K_ALIGN_SPLIT);
-  HIP_OK(c, sst::launch_align_split(*a, t->args.w, t->n_rows, 2 * c->n_cu, c->stream));
+  if (int e = set_device(c)) return e;
+  Prof p(c, kid);
+  HIP_OK(c, sst::launch_align(split, *a, caps, t->args.w, t->n_rows, 2 * c->n_cu, c->stream));
   return SST_OK;
 }
 
@@ -3792,24 +3783,20 @@ static int align_caps_check(sst_table* t, const sst_align_args* a, const sst_ali
   return rc;
 }
 
+extern "C" int sst_align_windows_device(sst_table* t, const sst_align_args* a) {
+  return align_launch(align_args_check(t, a), t, a, nullptr, SST_K_ALIGN, false);
+}
+
+extern "C" int sst_align_split_device(sst_table* t, const sst_align_args* a) {
+  return align_launch(align_args_check(t, a), t, a, nullptr, SST_K_ALIGN_SPLIT, true);
+}
+
 extern "C" int sst_align_windows_caps_device(sst_table* t, const sst_align_args* a, const sst_align_caps* caps) {
-  if (int rc = align_caps_check(t, a, caps, "sst_align_windows_caps_device"); rc != 1) return rc;
-  sst_ctx* c = t->ctx;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  if (int rc = set_device(c)) return rc;
-  Prof p(c, SST_K_ALIGN_CAPS);
-  HIP_OK(c, sst::launch_align_windows_caps(*a, *caps, t->args.w, t->n_rows, 2 * c->n_cu, c->stream));
-  return SST_OK;
+  return align_launch(align_caps_check(t, a, caps, __func__), t, a, caps, SST_K_ALIGN_CAPS, false);
 }
 
 extern "C" int sst_align_split_caps_device(sst_table* t, const sst_align_args* a, const sst_align_caps* caps) {
-  if (int rc = align_caps_check(t, a, caps, "sst_align_split_caps_device"); rc != 1) return rc;
-  sst_ctx* c = t->ctx;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  if (int rc = set_device(c)) return rc;
-  Prof p(c, SST_K_ALIGN_SPLIT_CAPS);
-  HIP_OK(c, sst::launch_align_split_caps(*a, *caps, t->args.w, t->n_rows, 2 * c->n_cu, c->stream));
-  return SST_OK;
+  return align_launch(align_caps_check(t, a, caps, __func__), t, a, caps, SST_K_ALIGN_SPLIT_CAPS, true);
 }
 
 extern "C" int sst_skeleton_alpha_device(sst_table* t, int64_t n_spec, const int32_t* d_max_len,

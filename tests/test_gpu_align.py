@@ -11,28 +11,13 @@ import numpy as np
 import pytest
 
 import _align_cases as AC
+import _align_gpu as AG
+from _align_gpu import CHUNK, K, engine, full_table  # noqa: F401
 from conftest import load_golden
 
 pytestmark = pytest.mark.gpu
 TOL, PREC = 0.02, 0.5  # the small alphabets' (W = ceil(0.04 obs))
 WAVES = 4              # waves of a k_align_windows workgroup
-CHUNK = 384            # fragment records the kernel holds at a time
-
-
-@pytest.fixture(scope="module")
-def engine():
-    from spectrseqtools_amd import _native
-
-    return _native.get_engine(0)
-
-
-@pytest.fixture(scope="module")
-def K(engine):
-    from spectrseqtools_amd import alignment
-
-    k = int(engine._lib.sst_align_capacity())
-    assert k == alignment.ALIGN_CAPACITY and k >= 1024
-    return k
 
 
 @pytest.fixture(scope="module")
@@ -56,27 +41,9 @@ def small_tables(engine):
         t.device_table.close()
 
 
-@pytest.fixture(scope="module")
-def full_table(engine):
-    from spectrseqtools_amd.mass_table import DynamicProgrammingTable, SequenceInformation
-    from spectrseqtools_amd.masses import EXPLANATION_MASSES, MATCHING_THRESHOLD, TOLERANCE
-
-    seq = SequenceInformation(max_len=20, su_mass=3000.0, obs_mass=3500.0, modification_rate=0.5)
-    dp = DynamicProgrammingTable(EXPLANATION_MASSES, compression_rate=32, tolerance=MATCHING_THRESHOLD,
-                                 precision=TOLERANCE, seq=seq, engine=engine)
-    yield dp
-    dp.close()
-
-
 def both(dp, specs, row_mass, K):
     """(device, host at capacity K) certificates of a case; asserts them equal."""
-    from spectrseqtools_amd import alignment
-
-    o = AC.make_outcome(specs, row_mass)
-    host = alignment.align_host(o, dp.tolerance, dp.precision, K)
-    dev = alignment.align_device(dp, o)
-    assert np.array_equal(dev.frag_off, o.frag_off)
-    AC.assert_equal(dev, (host.status, host.alignable, host.n_fit, host.first), row_mass[:8])
+    _, dev, host = AG.run(dp, specs, row_mass, K)
     return dev, host
 
 

@@ -1,6 +1,6 @@
 """GPU tests of the alignment certificate under the universal modification cap
 (sst_align_windows_caps_device, sst_align_split_caps_device: k_align_windows_caps
-and k_align_split_caps in csrc/sst_align_caps.hip; alignment.align_device(caps=),
+and k_align_split_caps in csrc/sst_align.hip; alignment.align_device(caps=),
 run_batch(align_caps=True)): the device result equals alignment.align_host(...,
 caps=...) in all four outputs -- on random small spectra with mixed caps, where
 the smallest mass of a position is the modified row's, at the capacity's edge of
@@ -14,55 +14,19 @@ import pytest
 
 import _align_caps_cases as CC
 import _align_cases as AC
+import _align_gpu as AG
+from _align_gpu import (FIELDS, OBS_W, K, device_args, edge_positions, engine, full_table,  # noqa: F401
+                        prefix_counts, window_frags)
 from conftest import load_golden
-from test_gpu_align_split import OBS_W, device_args, edge_positions, prefix_counts, window_frags
 
 pytestmark = pytest.mark.gpu
-FIELDS = ("status", "alignable", "n_fit", "first")
 START = AC.code_of(True, False)
-
-
-@pytest.fixture(scope="module")
-def engine():
-    from spectrseqtools_amd import _native
-
-    return _native.get_engine(0)
-
-
-@pytest.fixture(scope="module")
-def K(engine):
-    from spectrseqtools_amd import alignment
-
-    k = int(engine._lib.sst_align_capacity())
-    assert k == alignment.ALIGN_CAPACITY and k >= 1024 and k % 4 == 0
-    return k
-
-
-@pytest.fixture(scope="module")
-def full_table(engine):
-    from spectrseqtools_amd.mass_table import DynamicProgrammingTable, SequenceInformation
-    from spectrseqtools_amd.masses import EXPLANATION_MASSES, MATCHING_THRESHOLD, TOLERANCE
-
-    seq = SequenceInformation(max_len=20, su_mass=3000.0, obs_mass=3500.0, modification_rate=0.5)
-    dp = DynamicProgrammingTable(EXPLANATION_MASSES, compression_rate=32, tolerance=MATCHING_THRESHOLD,
-                                 precision=TOLERANCE, seq=seq, engine=engine)
-    for w, obs in OBS_W.items():
-        assert math.ceil(dp.tolerance * obs / dp.precision) == w
-    yield dp
-    dp.close()
 
 
 def run(dp, specs, rm, K, caps, split=True):
     """(outcome, device, host) of a case under `caps`; asserts the device equal
     to the host model at capacity K in all four outputs."""
-    from spectrseqtools_amd import alignment
-
-    o = AC.make_outcome(specs, rm)
-    host = alignment.align_host(o, dp.tolerance, dp.precision, K, split=split, caps=caps)
-    dev = alignment.align_device(dp, o, split=split, caps=caps)
-    assert np.array_equal(dev.frag_off, o.frag_off)
-    AC.assert_equal(dev, tuple(getattr(host, k) for k in FIELDS), ("split", split))
-    return o, dev, host
+    return AG.run(dp, specs, rm, K, split=split, caps=caps)
 
 
 def capped_counts(spec, rm, row_mod, E):
