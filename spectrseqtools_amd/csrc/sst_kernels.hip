@@ -327,6 +327,31 @@ __global__ __launch_bounds__(256) void k_is_valid(ValidArgs v) {
 // lane per peak: the peak's mass is read once (8 B instead of 16 B per
 // query) and its NW windows are quantised together, so their bitset loads
 // are in flight at once.
+// (peak_window: one window of a peak classified.  look: the answer needs the
+// bitset over [a, b], and is `code` when no bit is set there; otherwise the
+// answer is `code` and [a, b] is empty.  is_valid_peak classifies a window
+// into this record and then reads the bitset on one condition, `look`: the
+// fused step's is_valid workgroups run beside the scan faster in this form
+// than with the window's flags tested where they are used, same-box A/B,
+// DESIGN §5.)
+struct PeakWindow {
+  uint32_t a, b;
+  bool look;
+  int8_t code;
+};
+__device__ __forceinline__ PeakWindow peak_window(const ValidArgs& v, const double shift, const double obs,
+                                                  const double t, const double bmax) {
+  double lof, hif;
+  quantise_lean(obs - shift, t, v.prec, v.rprec, lof, hif);
+  const double af = __builtin_fmax(lof, 1.0);
+  const bool act = lof <= hif && af <= hif;
+  const double bf = __builtin_fmin(hif, bmax);
+  const bool inr = act && af <= bf;
+  const bool full = inr && bf >= (double)v.full_lo && af < (double)v.full_hi;
+  const bool look = inr && !full && bf >= (double)v.first_reach;
+  const int8_t miss = act && hif >= (double)v.limit ? (int8_t)-1 : (int8_t)0;
+  return {look ? (uint32_t)af : 1u, look ? (uint32_t)bf : 0u, look, full ? (int8_t)1 : miss};
+}
 template <int NW>
 __device__ __forceinline__ void is_valid_peak(const ValidArgs& v, const PeakShifts& sh, const uint32_t p) {
   if (p >= (uint32_t)v.n) return;
@@ -335,16 +360,9 @@ __device__ __forceinline__ void is_valid_peak(const ValidArgs& v, const PeakShif
   const double bmax = (double)(v.limit - 1);
 #pragma unroll
   for (int k = 0; k < NW; ++k) {
-    double lof, hif;
-    quantise_lean(obs - sh.shift[k], t, v.prec, v.rprec, lof, hif);
-    const double af = __builtin_fmax(lof, 1.0);
-    const bool act = lof <= hif && af <= hif;
-    const double bf = __builtin_fmin(hif, bmax);
-    const bool inr = act && af <= bf;
-    const bool full = inr && bf >= (double)v.full_lo && af < (double)v.full_hi;
-    bool hit = full;
-    if (inr && !full && bf >= (double)v.first_reach) hit = any_bits(v.valid, (uint32_t)af, (uint32_t)bf);
-    v.out[(size_t)k * v.n + p] = hit ? (int8_t)1 : (act && hif >= (double)v.limit ? (int8_t)-1 : (int8_t)0);
+    const PeakWindow w = peak_window(v, sh.shift[k], obs, t, bmax);
+    const bool hit = w.look && any_bits(v.valid, w.a, w.b);
+    v.out[(size_t)k * v.n + p] = hit ? (int8_t)1 : w.code;
   }
 }
 template <int NW>
@@ -2231,7 +2249,10 @@ __global__ __launch_bounds__(kScanWG, 8) void k_explain_scan(ScanArgs a) {
 // the is_valid workgroups run in each CU's other half beside the scan from
 // the start, and the step pays one launch.  (is_valid in front of the scan
 // instead: 8 us slower per step; two scan workgroups per CU, is_valid only in
-// the scan's tail: 2 us slower; same-box A/Bs.)
+// the scan's tail: 2 us slower; two scan workgroups per CU whose waves each
+// do a slice of the is_valid work after their tiles, or before them: 8 and
+// 10 us slower -- is_valid is scattered-load throughput, free only beside the
+// scan's coalesced loads; same-box A/Bs)
 template <bool THR, bool MODS>
 __global__ __launch_bounds__(kScanWG, 8) void k_step(StepArgs a) {
   const uint32_t n_scan = gridDim.x - a.a7_blocks;
