@@ -1101,6 +1101,78 @@ int sst_align_windows_caps_device(sst_table* t, const sst_align_args* a, const s
  * stream.  Argument checks as sst_align_windows_caps_device. */
 int sst_align_split_caps_device(sst_table* t, const sst_align_args* a, const sst_align_caps* caps);
 
+/* Keep mode: the certificate's second side.  Everything of
+ * sst_align_windows_caps_device's definition stays; status, alignable, n_fit
+ * and first equal its outputs bit for bit.  Keep mode adds, per fragment, a
+ * proof that the program HAS a feasible point within the threshold (KEEP), so
+ * that the three answers are DROP (alignable == 0), KEEP (keep == 1) and
+ * SOLVE (the rest).
+ *   Inner window: with q = tol * obs / prec in f64 (the quotient W takes the
+ *     ceiling of), W_in = floor(q) - 1 if q is finite and >= 1, else -1
+ *     (nothing fits inside); clamped like W.  An integer sum s fits inside iff
+ *     |s - target| <= W_in.  Since |su / prec - target| <= 0.5, a sum that fits
+ *     inside has a true error <= (W_in + 0.5) prec <= tol * obs - prec / 2: the
+ *     margin is half a precision unit, the mirror image of the DROP side's.
+ *     W - W_in is 1 where q is an integer and 2 otherwise (q >= 1).
+ *   Per-row caps (linear_program.py:190-196): row_cap[L * n_rows + r] =
+ *     int(ceil(rate_r * L)) for L in [0, 253] and every table row r (n_rows the
+ *     table's), rate_r the modification_rate of the row of the explanation
+ *     masses that holds row r's first name; the caller computes it in f64 as
+ *     the reference does, the kernels see integers only.  n_r is the number of
+ *     positions i with r in A_i.  Row r of the spectrum's alphabet is free iff
+ *     row_cap >= n_r, or row_mod[r] != 0 and row_cap >= mod_cap[g] (all
+ *     modified rows together appear at most mod_cap times).  A spectrum is
+ *     row-free iff every row of alpha except row 0 (and rows the table does
+ *     not have) is free.  In a row-free spectrum every y within the universal
+ *     cap is within every per-row cap, so S_E(l, r) is exactly the program's
+ *     set of sums on [l, r].
+ *   Outputs:
+ *     keep        1 iff the spectrum is modelled, feasible and row-free, the
+ *                 fragment is not SKIPPED, and some closed admissible interval's
+ *                 S_E holds a sum that fits inside (the empty interval counts:
+ *                 it fits inside iff |target| <= W_in); else 0.
+ *     keep_first  l << 8 | r of the smallest such interval in (l, r) order (the
+ *                 empty one last, 0xFFFF); 0xFFFE if there is none.
+ *     spec_free   per spectrum: 1 iff it is modelled, feasible and row-free; 0
+ *                 else, and 0 for a spectrum without fragments (nothing is
+ *                 computed for it).
+ *   keep == 1 implies status == SST_ALIGN_FIT.
+ * What KEEP means: the program has a feasible point (y the choice behind the
+ * sum, x the interval) with error <= tol * obs - prec / 2, so a solve that
+ * runs to optimality returns a value within the threshold and filter_with_lp
+ * keeps the fragment.  A solver stopped by its time limit may return a worse
+ * incumbent, or none, and the reference then removes the fragment: KEEP equals
+ * the reference under completed solves only, while DROP holds under every
+ * outcome.  No solver runs in this project: the claim is proven and held to a
+ * brute force over every y and x, not solved.  keep == 0 promises nothing.
+ * One kernel (k_align_windows_keep: k_align_windows_caps with one more u32
+ * per fragment record, W - W_in in the record's spare bits, and the row test
+ * once per spectrum) on the ctx stream; no scratch buffer, no global atomics.
+ * All four members of keep are device pointers.  Argument checks and errors as
+ * sst_align_windows_caps_device, plus SST_E_ARG with a message for a NULL keep
+ * or, with n_spec > 0, a NULL member. */
+typedef struct sst_align_keep {
+  const int32_t* row_cap; /* [254 * table rows] */
+  uint8_t* keep;          /* outputs: [frag_off[n_spec]] */
+  uint16_t* keep_first;   /*          [frag_off[n_spec]] */
+  uint8_t* spec_free;     /*          [n_spec] */
+} sst_align_keep;
+int sst_align_windows_keep_device(sst_table* t, const sst_align_args* a, const sst_align_caps* caps,
+                                  const sst_align_keep* keep);
+
+/* The two-list split in keep mode: sst_align_split_caps_device's contract (a's
+ * outputs and keep's hold sst_align_windows_keep_device's result for the same
+ * arguments; only its SST_ALIGN_OPEN fragments are recomputed, every other
+ * keeps all six outputs bit for bit; idempotent on its own output; spec_free is
+ * read, not written).  For the recomputed fragments keep and keep_first come
+ * from the split-closed intervals of a row-free spectrum: some a, b of the two
+ * lists with |a + b - target| <= W_in and e_a + e_b <= E.  A fragment that was
+ * FIT at base keeps its keep and keep_first even where an inner fit exists only
+ * in an open interval: that incompleteness is documented, not fixed (keep == 0
+ * promises nothing).  One kernel (k_align_split_keep) on the ctx stream. */
+int sst_align_split_keep_device(sst_table* t, const sst_align_args* a, const sst_align_caps* caps,
+                                const sst_align_keep* keep);
+
 /* compute_sequence_length_bound (mass_table.py:343-487) after the skeleton's
  * alphabet reduction (skeleton_building.py:315-336), both directions, for
  * queries on per-spectrum reduced alphabets, exact without a table rebuild:
@@ -1225,7 +1297,9 @@ int64_t sst_pyset_order(const int32_t* keys, const int64_t* hashes, int64_t n, i
 #define SST_K_ALIGN_SPLIT 22 /* k_align_split (sst_align_split_device) */
 #define SST_K_ALIGN_CAPS 23 /* k_align_windows_caps (sst_align_windows_caps_device) */
 #define SST_K_ALIGN_SPLIT_CAPS 24 /* k_align_split_caps (sst_align_split_caps_device) */
-#define SST_K_COUNT 25
+#define SST_K_ALIGN_KEEP 25 /* k_align_windows_keep (sst_align_windows_keep_device) */
+#define SST_K_ALIGN_SPLIT_KEEP 26 /* k_align_split_keep (sst_align_split_keep_device) */
+#define SST_K_COUNT 27
 /* When enabled, every kernel launch of this ctx is bracketed by hipEvents
  * recorded on the ctx stream; sst_profile_read synchronises and returns the
  * summed milliseconds and launch counts per kernel id since the last read

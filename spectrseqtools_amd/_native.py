@@ -41,6 +41,7 @@ EXPORTS = (
     "sst_handoff_count_device", "sst_handoff_emit_device", "sst_table_scan_lds_hits", "sst_table_certify",
     "sst_align_capacity", "sst_align_windows_device", "sst_align_split_device",
     "sst_align_windows_caps_device", "sst_align_split_caps_device",
+    "sst_align_windows_keep_device", "sst_align_split_keep_device",
 )
 
 # kernel ids of sst_profile_read
@@ -53,7 +54,9 @@ K_ALIGN = 21
 K_ALIGN_SPLIT = 22
 K_ALIGN_CAPS = 23
 K_ALIGN_SPLIT_CAPS = 24
-K_COUNT = 25  # SST_K_COUNT
+K_ALIGN_KEEP = 25
+K_ALIGN_SPLIT_KEEP = 26
+K_COUNT = 27  # SST_K_COUNT
 KERNEL_NAMES = {K_IS_VALID: "k_is_valid", K_EXPLAIN_SCAN: "k_explain_scan", K_EXPLAIN_DEEP: "k_explain_deferred",
                 K_EXPLAIN_EXPAND: "k_explain_expand",
                 K_RESULT_PACK: "k_result_pack",  # ids 3, 4: reserved (merged into the deferred launch)
@@ -63,7 +66,8 @@ KERNEL_NAMES = {K_IS_VALID: "k_is_valid", K_EXPLAIN_SCAN: "k_explain_scan", K_EX
                 K_JACCARD: "k_jaccard", K_PAIRS_ALPHA: "k_pairs_alpha", K_REQUERY_MERGE: "k_requery_merge",
                 K_HANDOFF: "k_handoff", K_TABLE_CERTIFY: "k_table_certify", K_ALIGN: "k_align_windows",
                 K_ALIGN_SPLIT: "k_align_split", K_ALIGN_CAPS: "k_align_windows_caps",
-                K_ALIGN_SPLIT_CAPS: "k_align_split_caps"}
+                K_ALIGN_SPLIT_CAPS: "k_align_split_caps", K_ALIGN_KEEP: "k_align_windows_keep",
+                K_ALIGN_SPLIT_KEEP: "k_align_split_keep"}
 
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
@@ -126,6 +130,12 @@ class AlignArgs(ctypes.Structure):
 class AlignCaps(ctypes.Structure):
     """sst_align_caps (include/sst.h): the universal modification cap's two device arrays."""
     _fields_ = [("row_mod", ctypes.c_void_p), ("mod_cap", ctypes.c_void_p)]
+
+
+class AlignKeep(ctypes.Structure):
+    """sst_align_keep (include/sst.h): keep mode's per-row caps and its three output arrays (device)."""
+    _fields_ = [("row_cap", ctypes.c_void_p), ("keep", ctypes.c_void_p), ("keep_first", ctypes.c_void_p),
+                ("spec_free", ctypes.c_void_p)]
 
 
 # sst_align_windows_device's status per fragment (SST_ALIGN_*)
@@ -356,6 +366,9 @@ def load_library(path=LIB_PATH):
     lib.sst_align_split_device.restype = _I
     for f in (lib.sst_align_windows_caps_device, lib.sst_align_split_caps_device):
         f.argtypes = [_P, ctypes.POINTER(AlignArgs), ctypes.POINTER(AlignCaps)]
+        f.restype = _I
+    for f in (lib.sst_align_windows_keep_device, lib.sst_align_split_keep_device):
+        f.argtypes = [_P, ctypes.POINTER(AlignArgs), ctypes.POINTER(AlignCaps), ctypes.POINTER(AlignKeep)]
         f.restype = _I
     lib.sst_jaccard_device.argtypes = [_P, ctypes.POINTER(JaccardArgs)]
     lib.sst_jaccard_device.restype = _I

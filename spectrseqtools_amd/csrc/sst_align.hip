@@ -2,10 +2,11 @@
 // fragments of a spectrum no window of its skeleton can explain, the question
 // filter_with_lp (prediction.py:229-259) asks one LinearProgramInstance per
 // fragment (linear_program.py).  The definition is in include/sst.h
-// (sst_align_windows_device and the three entry points behind it).
+// (sst_align_windows_device and the five entry points behind it).
 //
 // Two kernel bodies, each compiled with and without the program's universal
-// modification cap (template parameter kCaps; Variant<> holds what differs):
+// modification cap (template parameter kCaps; Variant<> holds what differs),
+// and under the cap also in keep mode (kKeep, below):
 //
 //   align_windows  k_align_windows, k_align_windows_caps: one spectrum per
 //                  workgroup, persistent grid over spectra.
@@ -82,8 +83,21 @@
 //   k_align_windows_caps  the bytes raise a wave's lists to 20 KiB: 3 waves,
 //                         60 + 15.2 = 75.2 KiB (4 waves: 80 + 15, one workgroup)
 //   k_align_split_caps    25 KiB a wave: 2 waves, 50 + 18.2 = 68.2 KiB
+//   k_align_windows_keep, k_align_split_keep: the caps kernels' + 1.5 KiB
 // Every global store is a plain vector store of an output element; the only
 // atomics are LDS atomics.
+//
+// Keep mode (a third compile-time axis, kKeep, which requires kCaps: k_align_
+// windows_keep, k_align_split_keep; nothing of it is decided at run time in the
+// four kernels above).  Once per spectrum, one row per thread counts n_r, the
+// positions whose set holds the row, and tests it against row_cap[L * n_rows +
+// r]: the spectrum is row-free iff every row of alpha is free (the split reads
+// the base kernel's spec_free instead).  A record carries W - W_in in two spare
+// bits of f_meta and one more word, f_keep: where the search for W hits in a
+// row-free spectrum, the first entry >= target - W_in - LO is at most two
+// entries further (distinct integers, W - W_in <= 2), and if it is <= target +
+// W_in - LO the interval joins f_keep by an LDS min.  The split's walk over B
+// goes on until an entry within budget also lies in the inner window.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -129,11 +143,18 @@ struct CapsLds {  // behind AlignLds / SplitLds, under the cap only
   uint8_t p_flag[256];        // per position: 1 forced, 2 the smallest mass pays
 };
 
-// What differs between the four kernels, at compile time: the waves of a
+struct KeepLds {  // behind CapsLds, in keep mode only
+  uint32_t f_keep[kAlignF];  // per record: l << 8 | r of the smallest interval with an inner fit
+  uint32_t row_bad;          // some row of alpha is not free
+  uint32_t pad;
+};
+
+// What differs between the six kernels, at compile time: the waves of a
 // workgroup, the bytes of a wave's slice of lists and the LDS structs behind them.
-template <bool kSplit_, bool kCaps_>
+template <bool kSplit_, bool kCaps_, bool kKeep_ = false>
 struct Variant {
-  static constexpr bool kSplit = kSplit_, kCaps = kCaps_;
+  static constexpr bool kSplit = kSplit_, kCaps = kCaps_, kKeep = kKeep_;
+  static_assert(kCaps || !kKeep, "keep mode decides on the capped lists");
   static constexpr int kWaves = kSplit ? (kCaps ? 2 : 3) : (kCaps ? 3 : 4);
   static constexpr int kWG = 64 * kWaves;
   static constexpr int kLists = kSplit ? 5 : 4;  // K entries each: A, B (the split: B's two), 2 K of merge temp
@@ -141,11 +162,13 @@ struct Variant {
   using Records = std::conditional_t<kSplit, SplitLds, AlignLds>;
   static constexpr size_t kRecordsAt = (size_t)kWaves * kWaveBytes;
   static constexpr size_t kCapsAt = kRecordsAt + sizeof(Records);
-  static constexpr size_t kLdsBytes = kCapsAt + (kCaps ? sizeof(CapsLds) : 0);
+  static constexpr size_t kKeepAt = kCapsAt + sizeof(CapsLds);
+  static constexpr size_t kLdsBytes = kCapsAt + (kCaps ? sizeof(CapsLds) : 0) + (kKeep ? sizeof(KeepLds) : 0);
   static_assert(2 * kLdsBytes <= kCuLdsBytes, "two workgroups per CU");
   static_assert(!kCaps || (size_t)(kWaves + 1) * kWaveBytes + sizeof(Records) > kCuLdsBytes / 2,
                 "one more wave would cost the second workgroup");
-  static_assert(kWaveBytes % 8 == 0 && sizeof(Records) % 8 == 0, "the records behind the lists stay aligned");
+  static_assert(kWaveBytes % 8 == 0 && sizeof(Records) % 8 == 0 && sizeof(CapsLds) % 8 == 0,
+                "the records behind the lists stay aligned");
   static_assert(!kSplit || (kAlignF >= kWG && kWaves <= 3),
                 "a chunk takes at least one block of the status scan; SplitLds serves every split workgroup");
 };
@@ -181,6 +204,11 @@ struct AlignCapsKArgs {
   sst_align_caps c;
 };
 
+struct AlignKeepKArgs {
+  AlignCapsKArgs kc;
+  sst_align_keep kp;
+};
+
 template <bool kCaps>
 struct CapState {};
 template <>
@@ -188,6 +216,8 @@ struct CapState<true> {
   const uint8_t* p_flag;  // CapsLds::p_flag
   uint64_t mod0, mod1;    // the table's modified rows
   uint32_t E;             // the spectrum's budget beyond its forced positions
+  uint32_t* f_keep;       // KeepLds::f_keep            (these two: set and read in keep mode only)
+  bool row_free;          // every row of alpha is free: S_E is the program's set of sums
 };
 
 template <bool kCaps>
@@ -317,8 +347,28 @@ __device__ __forceinline__ uint32_t budget(int cap, int forced) {
   return (uint32_t)(cap - forced < kAlignMaxLen ? cap - forced : kAlignMaxLen);
 }
 
+// floor(num / den) on the IEEE f64 quotient, as ceil_quot (sst_quant.h) takes the ceiling
+__device__ __forceinline__ double floor_quot(double num, double den, double rden) {
+  if (num == 0.0) return 0.0;
+  const double q = num * rden;
+  if (!(__builtin_fabs(q) < 0x1p40) || __builtin_fabs(q - __builtin_rint(q)) <= __builtin_fabs(q) * 0x1p-50)
+    return __builtin_floor(num / den);
+  return __builtin_floor(q);
+}
+
+// W - W_in of a fragment as f_meta's bits 4 - 5: 0 (both clamped), 1 (q an integer), 2; 3: W_in = -1, nothing fits
+// inside.  W_in = floor(q) - 1 for a finite q = tol * obs / prec >= 1, clamped like W.
+__device__ __forceinline__ uint32_t inner_code(double num, double prec, double rprec, int64_t w) {
+  const double f = floor_quot(num, prec, rprec);
+  if (!(f >= 1.0) || !(f <= 0x1.fffffffffffffp1023)) return 3u;
+  const int64_t w_in = f > 0x1p61 ? kAlignClamp : clamp_f(f) - 1;
+  return (uint32_t)(w - w_in);
+}
+
 // Record j of the chunk from fragment `at`: target, W, class / ends, cleared results; the chunk's flags and w_max.
-__device__ __forceinline__ void load_record(AlignLds& s, int j, int64_t at, const sst_align_args& a, double rprec, int L) {
+template <bool kKeep>
+__device__ __forceinline__ void load_record(AlignLds& s, uint32_t* f_keep, int j, int64_t at, const sst_align_args& a,
+                                            double rprec, int L) {
   const int64_t t = clamp_f(rint_quot(a.frag_su[at], a.prec, rprec));
   int64_t w = clamp_f(ceil_quot(a.tol * a.frag_obs[at], a.prec, rprec));
   if (w < 0) w = -1;  // a negative W: nothing fits (|s - target| <= W has no solution)
@@ -327,7 +377,12 @@ __device__ __forceinline__ void load_record(AlignLds& s, int j, int64_t at, cons
   const bool skipped = (cls == 1 || cls == 2) && (mn < 0 || mn >= L || mx < 0 || mx >= L);
   s.f_t[j] = t;
   s.f_w[j] = w;
-  s.f_meta[j] = cls | (skipped ? 4u : 0u) | (skipped ? 0u : ((uint32_t)mn & 0xffu) << 8 | ((uint32_t)mx & 0xffu) << 16);
+  uint32_t meta = cls | (skipped ? 4u : 0u) | (skipped ? 0u : ((uint32_t)mn & 0xffu) << 8 | ((uint32_t)mx & 0xffu) << 16);
+  if constexpr (kKeep) {
+    meta |= inner_code(a.tol * a.frag_obs[at], a.prec, rprec, w) << 4;
+    f_keep[j] = 0xffffffffu;
+  }
+  s.f_meta[j] = meta;
   s.f_nfit[j] = 0;
   s.f_first[j] = 0xffffffffu;
   s.f_open[j] = 0;
@@ -356,13 +411,17 @@ __device__ __forceinline__ uint32_t classes_present(AlignLds& s, int nf, int tid
 
 // One status for every fragment of a spectrum that is not modelled (SKIPPED) or has no alignment at all (INFEASIBLE).
 template <class V>
-__device__ __forceinline__ void write_spectrum(const sst_align_args& a, int64_t f0, int64_t nf_all, bool infeasible,
-                                               int tid) {
+__device__ __forceinline__ void write_spectrum(const sst_align_args& a, const sst_align_keep& kp, int64_t f0,
+                                               int64_t nf_all, bool infeasible, int tid) {
   for (int64_t j = tid; j < nf_all; j += V::kWG) {
     a.status[f0 + j] = infeasible ? SST_ALIGN_INFEASIBLE : SST_ALIGN_SKIPPED;
     a.alignable[f0 + j] = infeasible ? 0 : 1;
     a.n_fit[f0 + j] = 0;
     a.first[f0 + j] = 0xFFFE;
+    if constexpr (V::kKeep) {
+      kp.keep[f0 + j] = 0;
+      kp.keep_first[f0 + j] = 0xFFFE;
+    }
   }
 }
 
@@ -370,8 +429,9 @@ __device__ __forceinline__ void write_spectrum(const sst_align_args& a, int64_t 
 // split first + f_at[j] (a record SKIPPED there is not base-OPEN by the base
 // kernel's outputs: it is left as it is).
 template <class V>
-__device__ __forceinline__ void write_chunk(const AlignLds& s, const int64_t* f_at, const sst_align_args& a,
-                                            int64_t first, int nf, int tid) {
+__device__ __forceinline__ void write_chunk(const AlignLds& s, const uint32_t* f_keep, const int64_t* f_at,
+                                            const sst_align_args& a, const sst_align_keep& kp, int64_t first, int nf,
+                                            int tid) {
   for (int j = tid; j < nf; j += V::kWG) {
     const bool skipped = (s.f_meta[j] & 4u) != 0;
     if (V::kSplit && skipped) continue;
@@ -385,6 +445,11 @@ __device__ __forceinline__ void write_chunk(const AlignLds& s, const int64_t* f_
     a.alignable[at] = st != SST_ALIGN_NONE;
     a.n_fit[at] = n;
     a.first[at] = n ? (uint16_t)s.f_first[j] : (uint16_t)0xFFFE;
+    if constexpr (V::kKeep) {  // (a skipped record matches nothing: its word stays cleared)
+      const uint32_t kf = f_keep[j];
+      kp.keep[at] = kf != 0xffffffffu;
+      kp.keep_first[at] = kf != 0xffffffffu ? (uint16_t)kf : (uint16_t)0xFFFE;
+    }
   }
 }
 
@@ -430,8 +495,15 @@ __device__ __forceinline__ void cut_chunk(const AlignLds& s, int nf, const Inter
   j1 = cut ? lower_i64(s.f_t, nf, iv.hi + wm + 1) : nf;
 }
 
-// Every fragment of the chunk the interval is admissible for: fit / open.
-__device__ __forceinline__ void match_fragments(AlignLds& s, int nf, const Interval& iv, int mode, int L, int lane) {
+// Every fragment of the chunk the interval is admissible for: fit / open.  In
+// keep mode, f_keep of a row-free spectrum (else nullptr): also "fits inside".
+// The inner window lies d = W - W_in <= 2 inside the outer one at both ends and
+// the list's entries are distinct integers, so the first entry >= lo + d is at
+// most d entries behind the first >= lo: the second lower-bound search is a
+// walk of at most two steps from where the first one ended.
+template <bool kKeep>
+__device__ __forceinline__ void match_fragments(AlignLds& s, uint32_t* f_keep, int nf, const Interval& iv, int mode,
+                                                int L, int lane) {
   int j0, j1;
   cut_chunk(s, nf, iv, j0, j1);
   for (int j = j0 + lane; j < j1; j += 64) {
@@ -446,6 +518,14 @@ __device__ __forceinline__ void match_fragments(AlignLds& s, int nf, const Inter
     if (at < iv.n && (int64_t)iv.list[at] <= hi) {
       atomicAdd(&s.f_nfit[j], 1u);
       atomicMin(&s.f_first[j], (uint32_t)(iv.l << 8 | iv.r));
+      if constexpr (kKeep) {
+        const int64_t d = (int64_t)((s.f_meta[j] >> 4) & 3u);
+        if (f_keep && d != 3) {
+          int in = at;
+          while (in < iv.n && (int64_t)iv.list[in] < lo + d) ++in;
+          if (in < iv.n && (int64_t)iv.list[in] <= hi - d) atomicMin(&f_keep[j], (uint32_t)(iv.l << 8 | iv.r));
+        }
+      }
     }
   }
 }
@@ -455,7 +535,11 @@ __device__ __forceinline__ void match_fragments(AlignLds& s, int nf, const Inter
 // over the entries a of A that can take part, each searching B for the first
 // entry >= lo' - a (under the cap: from there for one within E - e_a); any
 // lane's hit is a fit.  A, B: offsets from LO_A, LO_B.
-template <bool kCaps>
+// In keep mode (under the cap), where the spectrum is row-free: the walk over
+// B's entries inside the window goes on until one within budget also lies
+// inside the inner window [lo + d, hi - d], and the fragment's entries of A
+// are taken until a pair fits inside or they are exhausted.
+template <bool kCaps, bool kKeep>
 __device__ __forceinline__ void match_split(AlignLds& s, int nf, const Interval& iv, const Spectrum<kCaps>& sp,
                                             List<kCaps> A, int nA, List<kCaps> B, int nB, int mode, int lane) {
   int j0, j1;
@@ -467,8 +551,15 @@ __device__ __forceinline__ void match_split(AlignLds& s, int nf, const Interval&
     const int i0 = lo - b_max > 0 ? lower_u32(A.v, nA, (uint32_t)(lo - b_max)) : 0;
     const int i1 = hi >= (int64_t)A.v[nA - 1] ? nA : upper_u32(A.v, nA, (uint32_t)hi);
     bool fit = false;
-    for (int c0 = i0; c0 < i1 && !fit; c0 += 64) {
+    [[maybe_unused]] bool inside = false, want = false;  // want: an inner fit is still looked for
+    [[maybe_unused]] int64_t d = 0;
+    if constexpr (kKeep) {
+      d = (int64_t)((s.f_meta[j] >> 4) & 3u);
+      want = sp.row_free && d != 3;
+    }
+    for (int c0 = i0; c0 < i1 && !(fit && !want); c0 += 64) {
       bool hit = false;
+      [[maybe_unused]] bool hit_in = false;
       const int i = c0 + lane;
       if (i < i1) {
         const int64_t x = (int64_t)A.v[i], need = lo - x;  // need <= b_max by i0
@@ -477,19 +568,36 @@ __device__ __forceinline__ void match_split(AlignLds& s, int nf, const Interval&
           for (int at = need > 0 ? lower_u32(B.v, nB, (uint32_t)need) : 0; at < nB && (int64_t)B.v[at] <= hi - x; ++at)
             if (B.e[at] <= left) {
               hit = true;
-              break;
+              if constexpr (kKeep) {
+                if (!want) break;
+                const int64_t b = (int64_t)B.v[at];
+                if (b >= need + d && b <= hi - x - d) {
+                  hit_in = true;
+                  break;
+                }
+              } else {
+                break;
+              }
             }
         } else {
           const int at = need > 0 ? lower_u32(B.v, nB, (uint32_t)need) : 0;
           hit = at < nB && (int64_t)B.v[at] <= hi - x;
         }
       }
-      fit = __ballot(hit) != 0;
+      fit = fit || __ballot(hit) != 0;
+      if constexpr (kKeep) {
+        if (want && __ballot(hit_in) != 0) {
+          inside = true;
+          want = false;
+        }
+      }
     }
     if (fit && lane == 0) {
       atomicAdd(&s.f_nfit[j], 1u);
       atomicMin(&s.f_first[j], (uint32_t)(iv.l << 8 | iv.r));
     }
+    if constexpr (kKeep)
+      if (inside && lane == 0) atomicMin(&sp.f_keep[j], (uint32_t)(iv.l << 8 | iv.r));
   }
 }
 
@@ -595,6 +703,13 @@ __device__ __forceinline__ void list_of_zero(List<kCaps> l, int lane) {
   wave_sync();
 }
 
+// f_keep where the spectrum is row-free, else (and outside keep mode) nullptr: nothing is kept
+template <class V>
+__device__ __forceinline__ uint32_t* keep_words(const Spectrum<V::kCaps>& sp) {
+  if constexpr (V::kKeep) return sp.row_free ? sp.f_keep : nullptr;
+  return nullptr;
+}
+
 // One sweep of a wave: positions `from`, from + dir, ... to the skeleton's end.
 template <class V>
 __device__ __forceinline__ void sweep(AlignLds& s, const Spectrum<V::kCaps>& sp, uint8_t* mine, int nf, int from,
@@ -616,7 +731,7 @@ __device__ __forceinline__ void sweep(AlignLds& s, const Spectrum<V::kCaps>& sp,
       if (n > kAlignK) iv.open = true; else iv.n = n;
       iv.list = cur.v;
     }
-    match_fragments(s, nf, iv, dir > 0 ? 0 : 1, sp.L, lane);
+    match_fragments<V::kKeep>(s, keep_words<V>(sp), nf, iv, dir > 0 ? 0 : 1, sp.L, lane);
   }
 }
 
@@ -662,9 +777,9 @@ __device__ __forceinline__ void sweep_split(AlignLds& s, const Spectrum<V::kCaps
       if (n > kAlignK) iv.open = true; else nB = n;
     }
     if (iv.open)
-      match_fragments(s, nf, iv, dir > 0 ? 0 : 1, L, lane);
+      match_fragments<false>(s, nullptr, nf, iv, dir > 0 ? 0 : 1, L, lane);  // (an open interval keeps nothing)
     else
-      match_split(s, nf, iv, sp, la, nA, lb, nB, dir > 0 ? 0 : 1, lane);
+      match_split<V::kCaps, V::kKeep>(s, nf, iv, sp, la, nA, lb, nB, dir > 0 ? 0 : 1, lane);
   }
 }
 
@@ -699,18 +814,45 @@ template <class V>
 struct Workgroup {  // the workgroup's dynamic LDS and a thread's place in it
   typename V::Records& rec;
   CapsLds* cl;  // (dereferenced under the cap only)
+  KeepLds* kl;  // (in keep mode only)
   int tid, lane, wave;
   uint8_t* mine;  // the wave's lists
   __device__ __forceinline__ explicit Workgroup(uint8_t* lds)
       : rec(*reinterpret_cast<typename V::Records*>(lds + V::kRecordsAt)),
         cl(reinterpret_cast<CapsLds*>(lds + V::kCapsAt)),
+        kl(reinterpret_cast<KeepLds*>(lds + V::kKeepAt)),
         tid((int)threadIdx.x), lane(tid & 63), wave(tid >> 6), mine(lds + wave * V::kWaveBytes) {}
 };
 
-// k_align_windows, k_align_windows_caps (c is read under the cap only)
-template <bool kCaps>
-__device__ __forceinline__ void align_windows(const AlignKArgs& k, const sst_align_caps& c) {
-  using V = Variant<false, kCaps>;
+// Keep mode, a modelled and feasible spectrum: is every row of alpha (row 0
+// excluded) free?  One row per thread, n_r counted over the positions' sets;
+// free iff row_cap >= n_r, or the row is modified and row_cap >= mod_cap (all
+// modified rows together appear at most mod_cap times).  row_bad is cleared
+// behind a barrier before; ends on a barrier.
+template <class V>
+__device__ __forceinline__ bool rows_free(KeepLds* kl, const Spectrum<true>& sp, const int32_t* row_cap, int n_rows,
+                                          int mod_cap, int tid) {
+  for (int r = 1 + tid; r < n_rows; r += V::kWG) {
+    const uint64_t bit = 1ull << (r & 63);
+    if (!((r < 64 ? sp.a0 : sp.a1) & bit)) continue;
+    int n_r = 0;
+    for (int p = 0; p < sp.L; ++p) {
+      uint64_t m0, m1;
+      position_set(sp, p, m0, m1);
+      n_r += ((r < 64 ? m0 : m1) & bit) != 0;
+    }
+    const int cap = row_cap[(int64_t)sp.L * n_rows + r];
+    const bool modified = ((r < 64 ? sp.mod0 : sp.mod1) & bit) != 0;
+    if (!(cap >= n_r || (modified && cap >= mod_cap))) atomicOr(&kl->row_bad, 1u);
+  }
+  __syncthreads();
+  return kl->row_bad == 0;
+}
+
+// k_align_windows, k_align_windows_caps, k_align_windows_keep (c is read under the cap only, kp in keep mode only)
+template <bool kCaps, bool kKeep = false>
+__device__ __forceinline__ void align_windows(const AlignKArgs& k, const sst_align_caps& c, const sst_align_keep& kp) {
+  using V = Variant<false, kCaps, kKeep>;
   extern __shared__ __attribute__((aligned(16))) uint32_t align_lds[];
   const Workgroup<V> wg(reinterpret_cast<uint8_t*>(align_lds));
   const sst_align_args& a = k.a;
@@ -719,10 +861,16 @@ __device__ __forceinline__ void align_windows(const AlignKArgs& k, const sst_ali
   Spectrum<kCaps> sp;
   uint64_t rows0, rows1;
   load_table<V>(s, wg.cl, k, c, tid, rows0, rows1, sp);
+  uint32_t* f_keep = nullptr;
+  if constexpr (kKeep) sp.f_keep = f_keep = wg.kl->f_keep;
 
   for (int64_t g = blockIdx.x; g < a.n_spec; g += gridDim.x) {
     const int64_t f0 = a.frag_off[g], nf_all = a.frag_off[g + 1] - f0;
-    if (nf_all <= 0) continue;
+    if (nf_all <= 0) {
+      if constexpr (kKeep)
+        if (tid == 0) kp.spec_free[g] = 0;  // (nothing is computed for a spectrum without fragments)
+      continue;
+    }
     const int64_t pos0 = a.pos_off[g], n_pos = a.pos_off[g + 1] - pos0;
     const int L = a.seq_len[g];
     sp.skel = a.skeleton + 2 * pos0;
@@ -733,6 +881,7 @@ __device__ __forceinline__ void align_windows(const AlignKArgs& k, const sst_ali
     if (tid == 0) {
       s.flags = 0;
       if constexpr (kCaps) wg.cl->n_forced = 0;
+      if constexpr (kKeep) wg.kl->row_bad = 0;
     }
     __syncthreads();
     const bool modelled = L >= 0 && L <= kAlignMaxLen && n_pos == (int64_t)L;
@@ -747,15 +896,21 @@ __device__ __forceinline__ void align_windows(const AlignKArgs& k, const sst_ali
       sp.E = budget(cap, n_forced);
     }
     if (!modelled || infeasible) {
-      write_spectrum<V>(a, f0, nf_all, infeasible, tid);
+      write_spectrum<V>(a, kp, f0, nf_all, infeasible, tid);
+      if constexpr (kKeep)
+        if (tid == 0) kp.spec_free[g] = 0;
       continue;
+    }
+    if constexpr (kKeep) {
+      sp.row_free = rows_free<V>(wg.kl, sp, kp.row_cap, k.n_rows, c.mod_cap[g], tid);
+      if (tid == 0) kp.spec_free[g] = sp.row_free;
     }
 
     for (int64_t c0 = 0; c0 < nf_all; c0 += kAlignF) {
       const int nf = (int)(nf_all - c0 < kAlignF ? nf_all - c0 : kAlignF);
       begin_chunk(s, tid);
       __syncthreads();
-      for (int j = tid; j < nf; j += V::kWG) load_record(s, j, f0 + c0 + j, a, k.rprec, L);
+      for (int j = tid; j < nf; j += V::kWG) load_record<kKeep>(s, f_keep, j, f0 + c0 + j, a, k.rprec, L);
       __syncthreads();
       const uint32_t present = classes_present<V>(s, nf, tid);
       // sweeps: t < L forward from t; t == L backward from L - 1; t == L + 1 the empty interval
@@ -768,19 +923,20 @@ __device__ __forceinline__ void align_windows(const AlignKArgs& k, const sst_ali
           const List<kCaps> zero = list_at<V>(wg.mine, 0);
           list_of_zero(zero, lane);
           const Interval iv{0xFF, 0xFF, 0, 0, false, zero.v, 1};
-          match_fragments(s, nf, iv, 2, L, lane);
+          match_fragments<kKeep>(s, keep_words<V>(sp), nf, iv, 2, L, lane);
         }
       }
       __syncthreads();
-      write_chunk<V>(s, nullptr, a, f0 + c0, nf, tid);
+      write_chunk<V>(s, f_keep, nullptr, a, kp, f0 + c0, nf, tid);
     }
   }
 }
 
-// k_align_split, k_align_split_caps: over the outputs of k_align_windows(_caps) (c is read under the cap only)
-template <bool kCaps>
-__device__ __forceinline__ void align_split(const AlignKArgs& k, const sst_align_caps& c) {
-  using V = Variant<true, kCaps>;
+// k_align_split, k_align_split_caps, k_align_split_keep: over the outputs of k_align_windows(_caps, _keep) (c is
+// read under the cap only, kp in keep mode only: spec_free is the base kernel's, the row test is not run again)
+template <bool kCaps, bool kKeep = false>
+__device__ __forceinline__ void align_split(const AlignKArgs& k, const sst_align_caps& c, const sst_align_keep& kp) {
+  using V = Variant<true, kCaps, kKeep>;
   extern __shared__ __attribute__((aligned(16))) uint32_t align_lds[];
   const Workgroup<V> wg(reinterpret_cast<uint8_t*>(align_lds));
   const sst_align_args& a = k.a;
@@ -790,6 +946,8 @@ __device__ __forceinline__ void align_split(const AlignKArgs& k, const sst_align
   Spectrum<kCaps> sp;
   uint64_t rows0, rows1;
   load_table<V>(s, wg.cl, k, c, tid, rows0, rows1, sp);
+  uint32_t* f_keep = nullptr;
+  if constexpr (kKeep) sp.f_keep = f_keep = wg.kl->f_keep;
 
   for (int64_t g = blockIdx.x; g < a.n_spec; g += gridDim.x) {
     const int64_t f0 = a.frag_off[g], nf_all = a.frag_off[g + 1] - f0;
@@ -804,6 +962,7 @@ __device__ __forceinline__ void align_split(const AlignKArgs& k, const sst_align
     sp.L = L;
     int cap = 0;
     if constexpr (kCaps) cap = c.mod_cap[g];
+    if constexpr (kKeep) sp.row_free = kp.spec_free[g] != 0;
     bool have_pos = false;
 
     for (int64_t next = 0; next < nf_all;) {
@@ -818,7 +977,7 @@ __device__ __forceinline__ void align_split(const AlignKArgs& k, const sst_align
         have_pos = true;
         for (int p = tid; p < L; p += V::kWG) position_range(s, wg.cl, sp, p);
       }
-      for (int j = tid; j < nf; j += V::kWG) load_record(s, j, f0 + sl.f_at[j], a, k.rprec, L);
+      for (int j = tid; j < nf; j += V::kWG) load_record<kKeep>(s, f_keep, j, f0 + sl.f_at[j], a, k.rprec, L);
       __syncthreads();
       // an empty A_i or F > mod_cap (never with a base-OPEN fragment): the spectrum is left as it is
       if (s.flags & 1u) break;
@@ -837,7 +996,7 @@ __device__ __forceinline__ void align_split(const AlignKArgs& k, const sst_align
         }
       }
       __syncthreads();
-      write_chunk<V>(s, sl.f_at, a, f0, nf, tid);
+      write_chunk<V>(s, f_keep, sl.f_at, a, kp, f0, nf, tid);
     }
   }
 }
@@ -847,15 +1006,26 @@ using Split = Variant<true, false>;
 using WindowsCaps = Variant<false, true>;
 using SplitCaps = Variant<true, true>;
 
+using WindowsKeep = Variant<false, true, true>;
+using SplitKeep = Variant<true, true, true>;
+
 __global__ __launch_bounds__(Windows::kWG) void k_align_windows(AlignKArgs k) {
-  align_windows<false>(k, sst_align_caps{});
+  align_windows<false>(k, sst_align_caps{}, sst_align_keep{});
 }
-__global__ __launch_bounds__(Split::kWG) void k_align_split(AlignKArgs k) { align_split<false>(k, sst_align_caps{}); }
+__global__ __launch_bounds__(Split::kWG) void k_align_split(AlignKArgs k) {
+  align_split<false>(k, sst_align_caps{}, sst_align_keep{});
+}
 __global__ __launch_bounds__(WindowsCaps::kWG) void k_align_windows_caps(AlignCapsKArgs kc) {
-  align_windows<true>(kc.k, kc.c);
+  align_windows<true>(kc.k, kc.c, sst_align_keep{});
 }
 __global__ __launch_bounds__(SplitCaps::kWG) void k_align_split_caps(AlignCapsKArgs kc) {
-  align_split<true>(kc.k, kc.c);
+  align_split<true>(kc.k, kc.c, sst_align_keep{});
+}
+__global__ __launch_bounds__(WindowsKeep::kWG) void k_align_windows_keep(AlignKeepKArgs kk) {
+  align_windows<true, true>(kk.kc.k, kk.kc.c, kk.kp);
+}
+__global__ __launch_bounds__(SplitKeep::kWG) void k_align_split_keep(AlignKeepKArgs kk) {
+  align_split<true, true>(kk.kc.k, kk.kc.c, kk.kp);
 }
 
 template <class V, class KArgs>
@@ -871,14 +1041,19 @@ hipError_t launch(void (*kernel)(KArgs), const KArgs& k, int64_t n_spec, int n_w
 
 }  // namespace
 
-hipError_t launch_align(bool split, const sst_align_args& a, const sst_align_caps* caps, const int* w, int n_rows,
-                        int n_wg, hipStream_t st) {
+hipError_t launch_align(bool split, const sst_align_args& a, const sst_align_caps* caps, const sst_align_keep* keep,
+                        const int* w, int n_rows, int n_wg, hipStream_t st) {
   if (a.n_spec <= 0) return hipSuccess;
   const AlignKArgs k{a, w, n_rows, 1.0 / a.prec};
   if (!caps)
     return split ? launch<Split>(k_align_split, k, a.n_spec, n_wg, st)
                  : launch<Windows>(k_align_windows, k, a.n_spec, n_wg, st);
   const AlignCapsKArgs kc{k, *caps};
+  if (keep) {
+    const AlignKeepKArgs kk{kc, *keep};
+    return split ? launch<SplitKeep>(k_align_split_keep, kk, a.n_spec, n_wg, st)
+                 : launch<WindowsKeep>(k_align_windows_keep, kk, a.n_spec, n_wg, st);
+  }
   return split ? launch<SplitCaps>(k_align_split_caps, kc, a.n_spec, n_wg, st)
                : launch<WindowsCaps>(k_align_windows_caps, kc, a.n_spec, n_wg, st);
 }

@@ -3763,14 +3763,15 @@ static int align_args_check(const sst_table* t, const sst_align_args* a) {
   return 1;
 }
 
-// Both checks passed (rc == 1): the launch of one of the four kernels under its profile id; else rc.
-static int align_launch(int rc, sst_table* t, const sst_align_args* a, const sst_align_caps* caps, int kid, bool split) {
+// Both checks passed (rc == 1): the launch of one of the six kernels under its profile id; else rc.
+static int align_launch(int rc, sst_table* t, const sst_align_args* a, const sst_align_caps* caps, int kid, bool split,
+                        const sst_align_keep* keep = nullptr) {
   if (rc != 1) return rc;
   sst_ctx* c = t->ctx;
   std::lock_guard<std::recursive_mutex> g(c->mu);
   if (int e = set_device(c)) return e;
   Prof p(c, kid);
-  HIP_OK(c, sst::launch_align(split, *a, caps, t->args.w, t->n_rows, 2 * c->n_cu, c->stream));
+  HIP_OK(c, sst::launch_align(split, *a, caps, keep, t->args.w, t->n_rows, 2 * c->n_cu, c->stream));
   return SST_OK;
 }
 
@@ -3797,6 +3798,26 @@ extern "C" int sst_align_windows_caps_device(sst_table* t, const sst_align_args*
 
 extern "C" int sst_align_split_caps_device(sst_table* t, const sst_align_args* a, const sst_align_caps* caps) {
   return align_launch(align_caps_check(t, a, caps, __func__), t, a, caps, SST_K_ALIGN_SPLIT_CAPS, true);
+}
+
+// align_caps_check, and the keep struct and its four members
+static int align_keep_check(sst_table* t, const sst_align_args* a, const sst_align_caps* caps, const sst_align_keep* keep,
+                            const char* who) {
+  if (!keep) return t ? fail(t->ctx, SST_E_ARG, std::string(who) + ": a NULL sst_align_keep") : SST_E_ARG;
+  const int rc = align_caps_check(t, a, caps, who);
+  if (rc == 1 && (!keep->row_cap || !keep->keep || !keep->keep_first || !keep->spec_free))
+    return fail(t->ctx, SST_E_ARG, std::string(who) + ": a NULL member of sst_align_keep");
+  return rc;
+}
+
+extern "C" int sst_align_windows_keep_device(sst_table* t, const sst_align_args* a, const sst_align_caps* caps,
+                                             const sst_align_keep* keep) {
+  return align_launch(align_keep_check(t, a, caps, keep, __func__), t, a, caps, SST_K_ALIGN_KEEP, false, keep);
+}
+
+extern "C" int sst_align_split_keep_device(sst_table* t, const sst_align_args* a, const sst_align_caps* caps,
+                                           const sst_align_keep* keep) {
+  return align_launch(align_keep_check(t, a, caps, keep, __func__), t, a, caps, SST_K_ALIGN_SPLIT_KEEP, true, keep);
 }
 
 extern "C" int sst_skeleton_alpha_device(sst_table* t, int64_t n_spec, const int32_t* d_max_len,

@@ -706,9 +706,10 @@ hipError_t launch_handoff_count(const sst_handoff_args& a, int n_wg, hipStream_t
 hipError_t launch_handoff_emit(const sst_handoff_args& a, int n_wg, hipStream_t st);
 // the alignment certificate (sst_align.hip): one spectrum per workgroup; w the table's row masses.  split: its
 // two-list split of the open intervals, over the outputs of the launch without (same arguments); caps: under the
-// universal modification cap, else NULL (k_align_windows, k_align_split, k_align_windows_caps, k_align_split_caps)
-hipError_t launch_align(bool split, const sst_align_args& a, const sst_align_caps* caps, const int* w, int n_rows,
-                        int n_wg, hipStream_t st);
+// universal modification cap, else NULL (k_align_windows, k_align_split, k_align_windows_caps, k_align_split_caps);
+// keep: keep mode (requires caps), else NULL (k_align_windows_keep, k_align_split_keep)
+hipError_t launch_align(bool split, const sst_align_args& a, const sst_align_caps* caps, const sst_align_keep* keep,
+                        const int* w, int n_rows, int n_wg, hipStream_t st);
 hipError_t launch_skel_alpha(int64_t n_spec, const int32_t* max_len, const uint64_t* skel_off, const uint64_t* skel,
                              const uint64_t* alpha, uint64_t canon0, uint64_t canon1, uint64_t* out, hipStream_t st);
 hipError_t launch_result_refs(const int8_t* status, int64_t n, const uint4* hits, uint64_t n_hits,

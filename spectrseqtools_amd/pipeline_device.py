@@ -1732,7 +1732,8 @@ def mirror_outcome(dp_table, obs, su_mass, seq_mass, max_len, breakage_dict, int
 
 def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=None, intensity=None,
               intensity_cutoff=0.5e6, mass_cutoff=50000, limits=DeviceLimits(), fallback="mirror", name_hash=None,
-              trim=True, explanation_masses=None, record=None, align=False, align_split=False, align_caps=False):
+              trim=True, explanation_masses=None, record=None, align=False, align_split=False, align_caps=False,
+              align_keep=False):
     """These spectra -> what Predictor.predict holds when it reaches its MILP
     stages (prediction.py:63-103), as a BatchOutcome: the six device stages
     (classify_device, fixpoint_device, bins_device, skeleton_device,
@@ -1776,7 +1777,13 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
     align_caps=True implies align and returns the certificate under the
     program's universal modification cap (align_device(caps=True) on the
     device's spectra, align_host(caps=lp_caps(...)) on the routed ones); it
-    combines with align_split."""
+    combines with align_split.
+    align_keep=True implies align_caps and returns the certificate in keep
+    mode (align_device(caps=True, keep=True) on the device's spectra,
+    align_host(caps=lp_caps(...), keep=lp_row_caps(...)) on the routed ones):
+    the AlignOutcome also carries keep, keep_first and spec_free
+    (alignment.lp_decisions: DROP / KEEP / SOLVE); it combines with
+    align_split."""
     from .masses import EXPLANATION_MASSES, TOLERANCE
     from .pipeline import max_len_of
 
@@ -1851,11 +1858,13 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
                                frag_max_end=h["max_end"], breakage_names=names, row_names=dev_out.row_names,
                                row_mass=dev_out.row_mass)
     m_idx = np.flatnonzero(reason)
+    align_caps = align_caps or align_keep
     align = align or align_split or align_caps
     if align:
         from . import alignment
 
-        dev_al = alignment.align_device(dp_table, dev_out, split=align_split, caps=bool(align_caps))
+        dev_al = alignment.align_device(dp_table, dev_out, split=align_split, caps=bool(align_caps),
+                                        keep=bool(align_keep))
     if not len(m_idx):
         return (dev_out, dev_al) if align else dev_out
     mirrored = [mirror_outcome(dp_table, obs[offsets[g]:offsets[g + 1]], su_seq[g], seq_mass[g], max_len[g],
@@ -1869,7 +1878,8 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
         cap = int(dp_table.device_table.engine._lib.sst_align_capacity())
         al = alignment.AlignOutcome.concat(
             [dev_al] + [alignment.align_host(o, dp_table.tolerance, dp_table.precision, cap, split=align_split,
-                                             caps=alignment.lp_caps(dp_table, o) if align_caps else None)
+                                             caps=alignment.lp_caps(dp_table, o) if align_caps else None,
+                                             keep=alignment.lp_row_caps(dp_table, o) if align_keep else None)
                         for o in mirrored])
         return both.take(where), al.take(where)
     return both.take(where)

@@ -50,7 +50,7 @@ GPU-busy share of its wall time.
 
 Usage: python tools/pipeline_bench.py [--spectra 100000] [--seed 7] [--host-driven]
        [--backend nccl|gloo] [--dump-outcomes DIR] [--as-rank R] [--handoff [--handoff-repeats 3]]
-       [--align | --align-split] [--align-caps] [--modification-rate 0.5]
+       [--align | --align-split] [--align-caps | --align-keep] [--modification-rate 0.5]
 """
 import argparse
 import json
@@ -299,7 +299,59 @@ def unconstrained_runs(out, spectra, free=None):
     return np.array(longest, dtype=np.int64), np.array(count, dtype=np.int64)
 
 
-def align_stage(pd, dp, rows, ln, post, kernels, split=False, caps=False):
+def keep_record(dp, out, al, split, kern):
+    """--align-keep: the three-way answer of the timed certificate `al` (keep
+    mode) -- the shares of DROP, KEEP and SOLVE over all fragments, the share of
+    row-free spectra among those with fragments -- and why a FIT fragment is
+    left without keep: its spectrum is not row-free; or it is and no sum of any
+    decided interval lies in the inner window (the fragment fits only in the
+    band between W_in and W); or one does, in a split-closed interval the split
+    did not visit (the fragment was FIT at base); or the inner window only
+    meets an undecided interval.  The last three come from an untimed caps
+    certificate (same split) of the same fragments with observed masses whose
+    W is the fragment's W_in."""
+    import copy
+
+    from spectrseqtools_amd import _native, alignment
+
+    tol, prec = float(dp.tolerance), float(dp.precision)
+    dec = alignment.lp_decisions(al)
+    n = max(1, len(dec))
+    n_frag = np.diff(out.frag_off)
+    spec_of = np.repeat(np.arange(len(n_frag)), n_frag)
+    has = n_frag > 0
+    q = tol * out.frag_obs / prec
+    w_in = np.where(np.isfinite(q) & (q >= 1), np.floor(q) - 1, -1.0)
+    inner = copy.copy(out)
+    inner.frag_obs = np.where(w_in >= 0, (w_in - 0.5) * prec / tol, -1.5 * prec / tol)  # ceil(q') == W_in (-1: nothing fits)
+    reproduced = bool((np.maximum(np.ceil(tol * inner.frag_obs / prec), -1.0) == w_in).all())
+    al_in = alignment.align_device(dp, inner, split=split, caps=True)
+    left = (al.status == _native.ALIGN_FIT) & (al.keep == 0)
+    free = al.spec_free[spec_of] != 0
+    n_left = max(1, int(left.sum()))
+    cause = {"spectrum_not_row_free": left & ~free,
+             "fits_only_between_w_in_and_w": left & free & (al_in.status == _native.ALIGN_NONE),
+             "inner_fit_in_an_interval_the_split_did_not_visit": left & free & (al_in.status == _native.ALIGN_FIT),
+             "inner_window_meets_an_undecided_interval_only": left & free & (al_in.status == _native.ALIGN_OPEN)}
+    return {"decision_shares": {name: float((dec == v).sum()) / n
+                                for name, v in (("DROP", alignment.LP_DROP), ("KEEP", alignment.LP_KEEP),
+                                                ("SOLVE", alignment.LP_SOLVE))},
+            "row_free_spectra_share": float(al.spec_free[has].mean()) if has.any() else 0.0,
+            "spectra_with_fragments": int(has.sum()),
+            "fit_share": float((al.status == _native.ALIGN_FIT).sum()) / n,
+            "fit_kept_share": float(((al.status == _native.ALIGN_FIT) & (al.keep != 0)).sum())
+            / max(1, int((al.status == _native.ALIGN_FIT).sum())),
+            "fit_without_keep": int(left.sum()),
+            "fit_without_keep_share_of_fit": float(left.sum()) / max(1, int((al.status == _native.ALIGN_FIT).sum())),
+            "fit_without_keep_by_cause": {k: float(v.sum()) / n_left for k, v in cause.items()},
+            "causes_cover_every_such_fragment": bool(sum(int(v.sum()) for v in cause.values()) == int(left.sum())),
+            "inner_window_reproduced": reproduced,
+            "keep_implies_fit": bool((al.status[al.keep != 0] == _native.ALIGN_FIT).all()),
+            "kernel_ms": {str(k): kern.get(_native.KERNEL_NAMES[k], (0.0, 0))[0]
+                          for k in (_native.K_ALIGN_KEEP, _native.K_ALIGN_SPLIT_KEEP)}}
+
+
+def align_stage(pd, dp, rows, ln, post, kernels, split=False, caps=False, keep=False):
     """--align: the alignment certificate (alignment.align_device) over the
     hand-off of the spectra the stages ran -- wall seconds from the host
     arrays in to the host arrays out (uploads, k_align_windows, downloads), the
@@ -315,7 +367,10 @@ def align_stage(pd, dp, rows, ln, post, kernels, split=False, caps=False):
     --align-split, k_align_split_caps); the split's base is then the caps base.
     The uncapped certificate of the same run (same split) is taken again,
     untimed, for its shares, the fragments the cap moved, the spectra it makes
-    INFEASIBLE and the mod_cap distribution ("caps")."""
+    INFEASIBLE and the mod_cap distribution ("caps").
+    --align-keep (keep=True, implies caps): the timed call runs in keep mode
+    (align_device(caps=True, keep=True): k_align_windows_keep and, with
+    --align-split, k_align_split_keep); "keep" holds keep_record's shares."""
     from spectrseqtools_amd import _native, alignment
 
     S = len(ln.seq_len)
@@ -330,7 +385,7 @@ def align_stage(pd, dp, rows, ln, post, kernels, split=False, caps=False):
                           breakage_names=rows.names, row_names=empty.row_names, row_mass=empty.row_mass)
     kernels()  # (the hand-off's launches are not this stage's)
     t0 = time.perf_counter()
-    al = alignment.align_device(dp, out, split=split, caps=caps)
+    al = alignment.align_device(dp, out, split=split, caps=caps, keep=keep)
     s = time.perf_counter() - t0
     kern = kernels()
     n = np.diff(out.frag_off)
@@ -363,6 +418,9 @@ def align_stage(pd, dp, rows, ln, post, kernels, split=False, caps=False):
                        "mod_cap_counts": {str(int(v)): int(c) for v, c in zip(*np.unique(mod_cap, return_counts=True))},
                        "kernel_ms": {str(k): kern.get(_native.KERNEL_NAMES[k], (0.0, 0))[0]
                                      for k in (_native.K_ALIGN_CAPS, _native.K_ALIGN_SPLIT_CAPS)}}
+    if keep:
+        rec["keep"] = keep_record(dp, out, al, split, kern)
+        kernels()
     if not split:
         return rec
     base = alignment.align_device(dp, out, caps=caps)  # untimed: what the split started from
@@ -390,7 +448,9 @@ def align_stage(pd, dp, rows, ln, post, kernels, split=False, caps=False):
                 "log2_combinations": pct([float(np.log2(np.maximum(x, 1)).sum()) for x in per])}
 
     unchanged = all(np.array_equal(getattr(al, k)[~was_open], getattr(base, k)[~was_open]) for k in al.FRAGMENT_FIELDS)
-    rec.update({"path": "device (sst_align_windows_caps_device + sst_align_split_caps_device), host arrays in and out"
+    rec.update({"path": "device (sst_align_windows_keep_device + sst_align_split_keep_device), host arrays in and out"
+                if keep else
+                "device (sst_align_windows_caps_device + sst_align_split_caps_device), host arrays in and out"
                 if caps else "device (sst_align_windows_device + sst_align_split_device), host arrays in and out",
                 "status_shares_base": base.shares(),
                 "open_decided_share": float((was_open & ~still).sum()) / n_open,
@@ -400,7 +460,8 @@ def align_stage(pd, dp, rows, ln, post, kernels, split=False, caps=False):
                 "not_alignable_share_base": float(1.0 - base.alignable.mean()) if len(base.status) else 0.0,
                 "other_fragments_unchanged": bool(unchanged),
                 "kernel_ms": {str(k): kern.get(_native.KERNEL_NAMES[k], (0.0, 0))[0]
-                              for k in ((_native.K_ALIGN_CAPS, _native.K_ALIGN_SPLIT_CAPS) if caps else
+                              for k in ((_native.K_ALIGN_KEEP, _native.K_ALIGN_SPLIT_KEEP) if keep else
+                                        (_native.K_ALIGN_CAPS, _native.K_ALIGN_SPLIT_CAPS) if caps else
                                         (_native.K_ALIGN, _native.K_ALIGN_SPLIT))},
                 "split_spectra": describe(was_open),  # the spectra k_align_split swept (a base-OPEN fragment)
                 "open_after_split": describe(still)})
@@ -453,12 +514,17 @@ def main():
                          "with --align-split.  The stage also reports the uncapped shares of the same run (untimed), "
                          "the fragments the cap moved (FIT -> NONE, OPEN -> FIT, OPEN -> NONE), the spectra it makes "
                          "INFEASIBLE and the mod_cap distribution")
+    ap.add_argument("--align-keep", action="store_true",
+                    help="--align-caps in keep mode (align_device(caps=True, keep=True)); alone or with --align-split.  "
+                         "The stage also reports the shares of DROP, KEEP and SOLVE, the share of row-free spectra, "
+                         "and the FIT fragments left without keep by cause (\"keep\")")
     ap.add_argument("--modification-rate", type=float, default=0.5,
                     help="the sequences' universal modification rate: the synthetic spectra's and the table's "
                          "SequenceInformation's (0.05: the low-modification-rate variant)")
     ap.add_argument("--as-rank", type=int, default=None,
                     help="single process: generate the spectra rank R of a multi-rank run would get")
     args = ap.parse_args()
+    args.align_caps = args.align_caps or args.align_keep
     args.align = args.align or args.align_split or args.align_caps
 
     import torch
@@ -553,7 +619,7 @@ def main():
         lw = pd.length_device(dp, kw, bw.alpha_dev, su_seq[:S0], batch.seq_mass[:S0], trim=False)
         pw = pd.post_skeleton_device(dp, rw, kw, lw)
         if args.align:
-            align_stage(pd, dp, rw, lw, pw, lambda: {}, split=args.align_split, caps=args.align_caps)
+            align_stage(pd, dp, rw, lw, pw, lambda: {}, split=args.align_split, caps=args.align_caps, keep=args.align_keep)
         # the reach buffer at length_device's batch budget, as a serving
         # process holds it: the timed stage allocates nothing (its hipMalloc /
         # hipFree of tens of GB took 0.1-3 s from run to run)
@@ -721,7 +787,8 @@ def main():
                                     + (f" ({'RCCL' if args.backend == 'nccl' else 'gloo'})" if dist else " (local)")}
     if rows is not None and args.align:
         barrier()
-        stages["align"] = align_stage(pd, dp, rows, ln, post, kernels, split=args.align_split, caps=args.align_caps)
+        stages["align"] = align_stage(pd, dp, rows, ln, post, kernels, split=args.align_split, caps=args.align_caps,
+                                      keep=args.align_keep)
         stages["align"]["s"] = tmax(stages["align"]["s"])
         busy(stages["align"])
         progress("align")
