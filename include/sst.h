@@ -514,33 +514,54 @@ int64_t sst_su_diff_queries(const double* su, const double* obs, const uint8_t* 
                             int64_t* spec, int8_t* kind, int64_t cap);
 /* ---- config 5 on the device ---------------------------------------------
  * classify_fragments and the filter_by_explanation fixpoint over many spectra
- * with every array in HBM.  Rows of spectrum g live in slots
- * 4 * d_peak_off[g] + i, i < d_rows[g] (d_rows_* arrays of 4 * n_peaks):
- * su, observed mass, meta = breakage | sides << 2 | is_singleton << 4 | peak
- * position << 8, alive.  Peaks in any order (ranked by mass on the device, equal
- * masses in their given order), <= 16383 per spectrum (above 4096 in the
- * reserved HBM slices); shifts / sides as sst_step_rows_device.  A spectrum of
- * more than 2048 rows is held in HBM slices the table's context reserves
- * (sst_pipe_reserve_rows, before the stages run); without them it is an
- * error.  d_err collects | 1 a spectrum over 16383 peaks (or over 4096 with
+ * with every array in HBM (the row slots: sst_row_slots).  Peaks in any order
+ * (ranked by mass on the device, equal masses in their given order), <= 16383
+ * per spectrum (above 4096 in the reserved HBM slices); shifts / sides as
+ * sst_step_rows_device.  A spectrum of more than 2048 rows is held in HBM
+ * slices the table's context reserves (sst_pipe_reserve_rows, before the
+ * stages run); without them it is an error.  d_err collects | 1 a spectrum over 16383 peaks (or over 4096 with
  * no slices reserved), 2 over 2048 rows with no slices reserved (or over
  * the reserved rows), 4 a window outside the pair class, 8 a window past a
  * table's end (the reference raises), 16 a dict too large for its hash, 32
  * rows out of mass order; the caller checks it. */
+/* The row slots: rows of spectrum g live in slots 4 * peak_off[g] + i,
+ * i < cnt[g] (su / obs / meta / alive: arrays of 4 * n_peaks).
+ * sst_classify_rows_device writes every array but peak_off (its input);
+ * sst_fix_round_device and sst_valid_rows_alpha_device write alive (the rows a
+ * round keeps); every other stage only reads.  An entry point may leave null
+ * the arrays it does not take: sst_valid_rows_alpha_device needs no meta,
+ * sst_fix_finish_device needs only cnt; all others need every array (with
+ * n_spec > 0).  Device pointers. */
+typedef struct sst_row_slots {
+  int64_t n_spec;
+  const int64_t* peak_off; /* [n_spec + 1] */
+  double* su;              /* standard-unit mass, ascending per spectrum */
+  double* obs;             /* observed mass */
+  uint32_t* meta;          /* breakage | sides << 2 | is_singleton << 4 | peak position << 8 */
+  uint8_t* alive;
+  uint32_t* cnt;           /* [n_spec] rows per spectrum */
+} sst_row_slots;
 /* Reserve the context's slices for spectra of up to max_rows rows (<= 65532:
  * 4 breakages x 16383 peaks) in the row stages (classify above 4096 peaks, fix
  * rounds, final dict, bins);
  * a no-op for max_rows <= 2048 or at most what is reserved.  Synchronises the
  * context's stream when it grows. */
 int sst_pipe_reserve_rows(sst_table* t, int64_t max_rows);
-/* classify_fragments (fragment_classification.py:17-101): A7 into d_valid_out
- * (may be NULL), the filters, is_singleton against t's masses, SU order. */
-int sst_classify_rows_device(sst_table* t, const double* d_obs, const int64_t* d_peak_off, int64_t n_spec,
-                             int64_t n_peaks, const double* d_intensity, double intensity_cutoff, double mass_cutoff,
-                             const double* d_su_seq, const double* shifts, const uint8_t* sides, int n_shifts,
-                             double max_weight, double tolerance, double precision, int8_t* d_valid_out,
-                             double* d_rows_su, double* d_rows_ob, uint32_t* d_rows_meta, uint8_t* d_alive,
-                             uint32_t* d_rows, uint32_t* d_err);
+/* classify_fragments (fragment_classification.py:17-101): A7 into valid_out,
+ * the filters, is_singleton against t's masses, SU order. */
+typedef struct sst_classify_args {
+  const double* obs;       /* [n_peaks] every spectrum's peaks (spectrum g: peak_off[g] .. peak_off[g + 1]) */
+  int64_t n_peaks;
+  const double* intensity; /* [n_peaks], may be NULL: no intensity filter */
+  double intensity_cutoff, mass_cutoff;
+  const double* su_seq;    /* [n_spec] SequenceInformation.su_mass */
+  const double* shifts;    /* [n_shifts] host: breakage weights * precision */
+  const uint8_t* sides;    /* [n_shifts] host: START = 1 | END = 2 per breakage */
+  int n_shifts;            /* 1 .. 4 */
+  double max_weight, tol, prec;
+  int8_t* valid_out;       /* may be NULL: the A7 codes [n_shifts * n_peaks], breakage-major */
+} sst_classify_args;
+int sst_classify_rows_device(sst_table* t, const sst_row_slots* rows, const sst_classify_args* a, uint32_t* d_err);
 /* Budget-binding ("exact mode") spectra of the device pipeline: a spectrum
  * whose max_modifications or modification caps are < 2 (a small
  * --modification_rate, or max_len <= 2: mass_explanation.py:158-172) can have
@@ -569,63 +590,74 @@ typedef struct sst_exact_io {
 } sst_exact_io;
 
 /* One filter_by_explanation round (prediction.py:170-202) of the spectra with
- * d_active[g]: their alive rows' window pairs and singletons explained
- * against d_alpha[2g..2g+1] (row masks of t; the caller keeps budgets from
+ * active[g]: their alive rows' window pairs and singletons explained
+ * against alpha[2g..2g+1] (row masks of t; the caller keeps budgets from
  * binding, see sst_explain_pairs_alpha), the explanation dict's surviving
- * entries, d_alpha_next = the canonical rows | (alphabet & observed rows),
- * d_active_next[g] = the alphabet shrank (*d_n_active, zeroed by the call, counts those);
- * d_rounds[g] += 1, d_queries[g] += the round's explain queries.  Settled
- * spectra carry their alphabet over. */
-int sst_fix_round_device(sst_table* t, const int64_t* d_peak_off, int64_t n_spec, const double* d_rows_su,
-                         const double* d_rows_ob, const uint32_t* d_rows_meta, uint8_t* d_alive,
-                         const uint32_t* d_rows, const uint64_t* d_alpha, uint64_t* d_alpha_next,
-                         const uint8_t* d_active, uint8_t* d_active_next, uint32_t* d_rounds, uint32_t* d_queries,
-                         uint32_t* d_n_active, double max_weight, double tolerance, double precision,
-                         uint32_t* d_err, const sst_exact_io* x);
+ * entries, alpha_next = the canonical rows | (alphabet & observed rows),
+ * active_next[g] = the alphabet shrank (*n_active, zeroed by the call, counts those);
+ * rounds[g] += 1, queries[g] += the round's explain queries.  Settled
+ * spectra carry their alphabet over.  Device pointers. */
+typedef struct sst_fix_args {
+  const uint64_t* alpha; /* [2 n_spec] */
+  uint64_t* alpha_next;  /* [2 n_spec] */
+  const uint8_t* active; /* [n_spec] */
+  uint8_t* active_next;  /* [n_spec] */
+  uint32_t* rounds;      /* [n_spec] */
+  uint32_t* queries;     /* [n_spec] */
+  uint32_t* n_active;
+  double max_weight, tol, prec; /* the round only */
+} sst_fix_args;
+int sst_fix_round_device(sst_table* t, const sst_row_slots* rows, const sst_fix_args* a, uint32_t* d_err,
+                         const sst_exact_io* x);
 /* The exact-mode spectra's half of the round, after their listed queries
- * were answered (same arrays as the round; x required). */
-int sst_fix_finish_device(sst_table* t, int64_t n_spec, const uint32_t* d_rows, const uint64_t* d_alpha,
-                          uint64_t* d_alpha_next,
-                          const uint8_t* d_active, uint8_t* d_active_next, uint32_t* d_rounds, uint32_t* d_queries,
-                          uint32_t* d_n_active, uint32_t* d_err, const sst_exact_io* x);
+ * were answered (same arrays as the round; of rows only cnt; x required). */
+int sst_fix_finish_device(sst_table* t, const sst_row_slots* rows, const sst_fix_args* a, uint32_t* d_err,
+                          const sst_exact_io* x);
 /* SkeletonBuilder._predict_skeleton's speculative bin queries
  * (skeleton_building.py:114-160; replaces the per-bin explain calls of
  * :131-160 for every spectrum at once) over the rows a fixpoint kept
- * (d_alive), on each spectrum's alphabet d_alpha: per side, bins are runs of
+ * (rows->alive), on each spectrum's alphabet alpha: per side, bins are runs of
  * rows whose SU step is <= tol * (obs_prev + obs); the side's first bin
  * explains its rows' SU masses against 0 (threshold tol * obs), every later
  * bin each (predecessor row, row) difference (tol * (obs_p + obs_r)); a
- * side's last bin only with >= 2 rows.  Two calls: count (d_n_q[S] queries
- * per spectrum, d_q_off[S + 1] their exclusive offsets, the total last), then
- * emit into d_status / d_count [total], spectrum-major (START side, then END;
+ * side's last bin only with >= 2 rows.  Two calls: count (n_q[S] queries
+ * per spectrum, q_off[S + 1] their exclusive offsets, the total last), then
+ * emit into status / count [total], spectrum-major (START side, then END;
  * bins in order; a bin's pairs predecessor-row-major).  Statuses SST_NONE /
  * EMPTY / SOME, or -10 for a window outside the pair class (hi >= 3 w_min:
- * the caller's general path).  With d_n_def non-null (zeroed by the caller),
+ * the caller's general path).  With n_def non-null (zeroed by the caller),
  * those windows are also listed, in any order, for
- * sst_explain_alpha_batch_device: d_def_mass / d_def_thr / d_def_spec /
- * d_def_q[*d_n_def] = window mass, threshold, spectrum and index into
- * d_status (capacity: the total).  d_err bit 2: a spectrum over 2048 rows
- * with no slices reserved (sst_pipe_reserve_rows). */
-int sst_bins_count_device(sst_table* t, const int64_t* d_peak_off, int64_t n_spec, const double* d_rows_su,
-                          const double* d_rows_ob, const uint32_t* d_rows_meta, const uint8_t* d_alive,
-                          const uint32_t* d_rows, double tol, uint32_t* d_n_q, uint64_t* d_q_off, uint32_t* d_err,
-                          uint32_t* d_n_q0 /* may be NULL: the START side's count per spectrum */);
-int sst_bins_emit_device(sst_table* t, const int64_t* d_peak_off, int64_t n_spec, const double* d_rows_su,
-                         const double* d_rows_ob, const uint32_t* d_rows_meta, const uint8_t* d_alive,
-                         const uint32_t* d_rows, const uint64_t* d_alpha, double tol, double prec,
-                         const uint64_t* d_q_off, int8_t* d_status, uint32_t* d_count, double* d_def_mass,
-                         double* d_def_thr, int32_t* d_def_spec, uint64_t* d_def_q, uint32_t* d_n_def,
-                         uint32_t* d_err, const uint8_t* d_pair_ok /* may be NULL; 0: list every window */);
+ * sst_explain_alpha_batch_device: def_mass / def_thr / def_spec /
+ * def_q[*n_def] = window mass, threshold, spectrum and index into
+ * status (capacity: the total).  d_err bit 2: a spectrum over 2048 rows
+ * with no slices reserved (sst_pipe_reserve_rows).  Device pointers.
+ * sst_bins_count_device reads tol and writes n_q, n_q0, q_off;
+ * sst_bins_emit_device reads every field but n_q, n_q0. */
+typedef struct sst_bins_args {
+  const uint64_t* alpha;  /* [2 n_spec] */
+  double tol, prec;
+  uint32_t* n_q;          /* [n_spec] */
+  uint32_t* n_q0;         /* may be NULL: the START side's count per spectrum */
+  uint64_t* q_off;        /* [n_spec + 1] */
+  int8_t* status;         /* [total] */
+  uint32_t* count;        /* [total] */
+  double* def_mass;
+  double* def_thr;
+  int32_t* def_spec;
+  uint64_t* def_q;
+  uint32_t* n_def;        /* may be NULL: the windows outside the pair class are not listed */
+  const uint8_t* pair_ok; /* may be NULL; 0: list every window */
+} sst_bins_args;
+int sst_bins_count_device(sst_table* t, const sst_row_slots* rows, const sst_bins_args* a, uint32_t* d_err);
+int sst_bins_emit_device(sst_table* t, const sst_row_slots* rows, const sst_bins_args* a, uint32_t* d_err);
 
 /* _reduce_alphabet's filter (prediction.py:211-227): is_valid_mass of the
  * alive rows of the d_active spectra against their reduced tables (d_alpha),
- * AND-ed into d_alive.  A spectrum whose alphabet did not change needs no
+ * AND-ed into rows->alive.  A spectrum whose alphabet did not change needs no
  * re-filter (its rows already passed that table), so a fixpoint passes the
- * round's changed flags (sst_fix_round_device's d_active_next). */
-int sst_valid_rows_alpha_device(sst_table* t, const int64_t* d_peak_off, int64_t n_spec, const double* d_rows_su,
-                                const double* d_rows_ob, const uint32_t* d_rows, const uint64_t* d_alpha,
-                                const uint8_t* d_active, uint8_t* d_alive, double tolerance, double precision,
-                                uint32_t* d_err);
+ * round's changed flags (sst_fix_args.active_next).  rows->meta is not read. */
+int sst_valid_rows_alpha_device(sst_table* t, const sst_row_slots* rows, const uint64_t* d_alpha,
+                                const uint8_t* d_active, double tolerance, double precision, uint32_t* d_err);
 
 /* The explanation dict collect_diff_explanations_for_su builds per spectrum
  * (prediction.py:261-284): spectrum g's queries [offsets[g], offsets[g+1])
@@ -764,24 +796,28 @@ int sst_skel_walk_device(sst_table* t, const sst_walk_args* a);
  * payload record (SOME; else 0).  Valid while the result lives unchanged. */
 int sst_result_refs_device(sst_result* r, const int64_t* d_dst, uint64_t* d_ptr, uint32_t* d_n, int8_t* d_st);
 /* filter_by_explanation's final explanation dict per spectrum
- * (prediction.py:261-329 over the final rows and alphabet).  Count pass:
- * d_n_q[g] = the last round's queries, d_off = their exclusive offsets
- * (n_spec + 1 entries, total last); build pass: keys ascending (double bits)
- * and the last writer's threshold into [d_off[g], + d_n_ent[g]). */
-int sst_dict_count_device(sst_table* t, const int64_t* d_peak_off, int64_t n_spec, const double* d_rows_su,
-                          const double* d_rows_ob, const uint32_t* d_rows_meta, const uint8_t* d_alive,
-                          const uint32_t* d_rows, double max_weight, double tol, uint32_t* d_n_q, uint64_t* d_off,
-                          uint32_t* d_err);
-int sst_dict_build_device(sst_table* t, const int64_t* d_peak_off, int64_t n_spec, const double* d_rows_su,
-                          const double* d_rows_ob, const uint32_t* d_rows_meta, const uint8_t* d_alive,
-                          const uint32_t* d_rows, const uint64_t* d_alpha, double max_weight, double tol, double prec,
-                          const uint64_t* d_off, uint64_t* d_key, double* d_thr, uint32_t* d_n_ent, uint32_t* d_err,
+ * (prediction.py:261-329 over the final rows and alphabet).  Count pass
+ * (sst_dict_count_device; reads max_weight, tol): n_q[g] = the last round's
+ * queries, off = their exclusive offsets (n_spec + 1 entries, total last);
+ * build pass (sst_dict_build_device; every field but n_q): keys ascending
+ * (double bits) and the last writer's threshold into [off[g], + n_ent[g]).
+ * sst_dict_list_device (reads max_weight, tol; x required): the exact-mode
+ * spectra's final-round queries listed for the masked explain (before
+ * sst_dict_build_device, which then reads x->xa_*).  Device pointers. */
+typedef struct sst_dict_args {
+  const uint64_t* alpha; /* [2 n_spec] */
+  double max_weight, tol, prec;
+  uint32_t* n_q;         /* [n_spec] */
+  uint64_t* off;         /* [n_spec + 1] */
+  uint64_t* key;         /* [total] */
+  double* thr;           /* [total] */
+  uint32_t* n_ent;       /* [n_spec] */
+} sst_dict_args;
+int sst_dict_count_device(sst_table* t, const sst_row_slots* rows, const sst_dict_args* a, uint32_t* d_err);
+int sst_dict_build_device(sst_table* t, const sst_row_slots* rows, const sst_dict_args* a, uint32_t* d_err,
                           const sst_exact_io* x);
-/* The exact-mode spectra's final-round queries listed for the masked
- * explain (before sst_dict_build_device, which then reads x->xa_*). */
-int sst_dict_list_device(sst_table* t, const int64_t* d_peak_off, int64_t n_spec, const double* d_rows_su,
-                         const double* d_rows_ob, const uint32_t* d_rows_meta, const uint8_t* d_alive,
-                         const uint32_t* d_rows, double max_weight, double tol, uint32_t* d_err, const sst_exact_io* x);
+int sst_dict_list_device(sst_table* t, const sst_row_slots* rows, const sst_dict_args* a, uint32_t* d_err,
+                         const sst_exact_io* x);
 
 /* select_sequence_length_with_jaccard (skeleton_building.py:315-370) and
  * combine_skeleton_sequences (:494-516) per spectrum, one lane each: the
@@ -1181,35 +1217,48 @@ int sst_align_split_keep_device(sst_table* t, const sst_align_args* a, const sst
  * d_bits[d_off[g] + k * d_words[g] + m / 32] <=> m is a sum of kept rows up
  * to that one (the rebuilt table's pair(r_k, m) != 0), for m < 32 d_words[g]
  * (>= the highest window value + 1).  sst_length_bounds_reach_device then
- * replays the reference's memoised DFS once per query (spectrum d_spec[i])
- * on those pairs and derives both bounds from it: d_lower[i] / d_upper[i],
- * d_status[i] 0 ok, SST_OUT_OF_TABLE (the reference raises), SST_ABORTED (a
- * window in the reduced table's masked last word, or a guard), -5 an empty
- * window.  Budgets: max_len, max_mods and the table's caps
- * (sst_table_set_budgets) as in sst_length_bound_batch -- or, with d_qlen
- * non-NULL, per query: max_len d_qlen[i], caps d_caps_len[d_qlen[i] *
- * SST_MAX_ROWS + r] and max_mods d_a0_len[d_qlen[i]] (the caller's
- * round(L * rate)), so spectra of every max_len share one launch (the
- * table's is_modification flags still come from sst_table_set_budgets).
- * d_nodes (may be NULL; zeroed by the caller): per query, the replay's
- * visited nodes summed over its attempts.  soft_nodes > 0: a query whose
- * replay passes that many nodes stops with status SST_LB_HEAVY (the caller
- * replays such queries together later, with soft_nodes 0), so that a few
- * heavy spectra do not hold up a batch.  memo_first: the first attempt's
+ * replays the reference's memoised DFS once per query (sst_length_queries)
+ * on those pairs and derives both bounds from it.  soft_nodes > 0: a query
+ * whose replay passes that many nodes stops with status SST_LB_HEAVY (the
+ * caller replays such queries together later, with soft_nodes 0), so that a
+ * few heavy spectra do not hold up a batch.  memo_first: the first attempt's
  * memo masses per query (0: 2^16; a power of two).  fuse: both bounds'
  * values computed inside the replay, in dense per-mass slots (allowed when
  * every alphabet has <= 64 kept rows; 0: the separate value passes).
  * Device pointers. */
 #define SST_MAX_ROWS 120
 #define SST_LB_HEAVY (-7)
+/* The queries of both length-bound engines: query i is the window of su[i],
+ * obs[i] on the alphabet of spectrum spec[i].  Budgets: max_len, max_mods and
+ * the table's caps (sst_table_set_budgets) as in sst_length_bound_batch -- or,
+ * with qlen non-NULL, per query: max_len qlen[i], caps caps_len[qlen[i] *
+ * SST_MAX_ROWS + r] and max_mods a0_len[qlen[i]] (the caller's round(L *
+ * rate)), so spectra of every max_len share one launch (the table's
+ * is_modification flags still come from sst_table_set_budgets). */
+typedef struct sst_length_queries {
+  const double* su;        /* [n] */
+  const double* obs;       /* [n] */
+  const int32_t* spec;     /* [n] */
+  const uint64_t* alpha;   /* [2 n_spec] row masks */
+  int64_t n;
+  double tol, prec;
+  int max_len;
+  int64_t max_mods;
+  int64_t* lower;          /* [n] out: the bounds */
+  int64_t* upper;
+  int8_t* status;          /* [n] out: 0 ok, SST_OUT_OF_TABLE (the reference raises), SST_ABORTED (a window in the
+                              reduced table's masked last word, or a guard), SST_LB_EMPTY_WINDOW */
+  const int32_t* qlen;     /* [n] or NULL */
+  const int32_t* caps_len; /* required with qlen */
+  const int32_t* a0_len;   /* required with qlen */
+  uint64_t* nodes;         /* may be NULL; zeroed by the caller: per query, the replay's visited nodes summed
+                              over its attempts, or the memo entries the frontier creates */
+} sst_length_queries;
 int sst_reach_rows_device(sst_table* t, const uint64_t* d_alpha, const int64_t* d_words, const uint64_t* d_off,
                           int64_t n_spec, uint32_t* d_bits);
-int sst_length_bounds_reach_device(sst_table* t, const double* d_su, const double* d_obs, const int32_t* d_spec,
-                                   const uint64_t* d_alpha, const uint32_t* d_reach_bits, const uint64_t* d_reach_off,
-                                   const int64_t* d_reach_words, int64_t n, double tol, double prec, int max_len,
-                                   int64_t max_mods, int64_t* d_lower, int64_t* d_upper, int8_t* d_status,
-                                   const int32_t* d_qlen, const int32_t* d_caps_len, const int32_t* d_a0_len,
-                                   uint64_t* d_nodes, int64_t soft_nodes, uint32_t memo_first, int fuse);
+int sst_length_bounds_reach_device(sst_table* t, const sst_length_queries* q, const uint32_t* d_reach_bits,
+                                   const uint64_t* d_reach_off, const int64_t* d_reach_words, int64_t soft_nodes,
+                                   uint32_t memo_first, int fuse);
 
 /* The same bounds WITHOUT replaying the DFS (sst_frontier.hip, DESIGN §3
  * "first-visit frontier"): the reference's memo is keyed by (mass, row) and
@@ -1223,10 +1272,9 @@ int sst_length_bounds_reach_device(sst_table* t, const double* d_su, const doubl
  * sst_reach_lowest_device first turns sst_reach_rows_device's bitsets into one
  * byte per mass: d_lr[d_lr_off[g] + m] = the lowest kept rank k with m in
  * R_k (0xFF: none), m < 32 d_words[g] (d_lr_off[g] a multiple of 32).
- * sst_length_bounds_frontier_device: arguments as sst_length_bounds_reach_device
- * (d_lr / d_lr_off instead of the bitsets); d_nodes (may be NULL; zeroed by the
- * caller) = per query, the memo entries (distinct (mass, row) nodes) its DFS
- * creates.  workspace_bytes: the device workspace (0: half the free memory, at
+ * sst_length_bounds_frontier_device: the same queries (d_lr / d_lr_off instead
+ * of the bitsets); q->nodes = per query, the memo entries (distinct (mass, row)
+ * nodes) its DFS creates.  workspace_bytes: the device workspace (0: half the free memory, at
  * most 48 GB); queries are processed in chunks sized from the memo entries
  * per query seen so far (a chunk that overflows is split; a single query
  * beyond the workspace gets SST_ABORTED).
@@ -1249,12 +1297,8 @@ typedef struct sst_lbf_stats {
 } sst_lbf_stats;
 int sst_reach_lowest_device(sst_table* t, const uint64_t* d_alpha, const int64_t* d_words, const uint64_t* d_off,
                             int64_t n_spec, const uint32_t* d_bits, const uint64_t* d_lr_off, uint8_t* d_lr);
-int sst_length_bounds_frontier_device(sst_table* t, const double* d_su, const double* d_obs, const int32_t* d_spec,
-                                      const uint64_t* d_alpha, const uint8_t* d_lr, const uint64_t* d_lr_off, int64_t n,
-                                      double tol, double prec, int max_len, int64_t max_mods, int64_t* d_lower,
-                                      int64_t* d_upper, int8_t* d_status, const int32_t* d_qlen,
-                                      const int32_t* d_caps_len, const int32_t* d_a0_len, uint64_t* d_nodes,
-                                      uint64_t workspace_bytes, sst_lbf_stats* stats);
+int sst_length_bounds_frontier_device(sst_table* t, const sst_length_queries* q, const uint8_t* d_lr,
+                                      const uint64_t* d_lr_off, uint64_t workspace_bytes, sst_lbf_stats* stats);
 
 /* ---- CPython set order (the skeleton walk's emulation, sst_pyset.h) ---- */
 /* hash(tuple) of a tuple whose items hash to item_hashes[0..n) (CPython

@@ -98,6 +98,49 @@ class ExactIO(ctypes.Structure):
                 ("xa_n", ctypes.c_void_p), ("xa_ptr", ctypes.c_void_p)]
 
 
+class RowSlots(ctypes.Structure):
+    """sst_row_slots (include/sst.h): the row arrays classify writes and every later row stage reads."""
+    _fields_ = [("n_spec", ctypes.c_int64)] + \
+        [(n, ctypes.c_void_p) for n in ("peak_off", "su", "obs", "meta", "alive", "cnt")]
+
+
+class ClassifyArgs(ctypes.Structure):
+    """sst_classify_args (include/sst.h): classify_fragments' peaks and filters."""
+    _fields_ = [("obs", ctypes.c_void_p), ("n_peaks", ctypes.c_int64), ("intensity", ctypes.c_void_p),
+                ("intensity_cutoff", ctypes.c_double), ("mass_cutoff", ctypes.c_double), ("su_seq", ctypes.c_void_p),
+                ("shifts", ctypes.c_void_p), ("sides", ctypes.c_void_p), ("n_shifts", ctypes.c_int),
+                ("max_weight", ctypes.c_double), ("tol", ctypes.c_double), ("prec", ctypes.c_double),
+                ("valid_out", ctypes.c_void_p)]
+
+
+class FixArgs(ctypes.Structure):
+    """sst_fix_args (include/sst.h): one filter_by_explanation round's ping-pong arrays."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("alpha", "alpha_next", "active", "active_next", "rounds", "queries",
+                                               "n_active")] + \
+        [(n, ctypes.c_double) for n in ("max_weight", "tol", "prec")]
+
+
+class BinsArgs(ctypes.Structure):
+    """sst_bins_args (include/sst.h): the skeleton's speculative bin queries, count and emit."""
+    _fields_ = [("alpha", ctypes.c_void_p), ("tol", ctypes.c_double), ("prec", ctypes.c_double)] + \
+        [(n, ctypes.c_void_p) for n in ("n_q", "n_q0", "q_off", "status", "count", "def_mass", "def_thr", "def_spec",
+                                        "def_q", "n_def", "pair_ok")]
+
+
+class DictArgs(ctypes.Structure):
+    """sst_dict_args (include/sst.h): the final explanation dict, count, list and build."""
+    _fields_ = [("alpha", ctypes.c_void_p)] + [(n, ctypes.c_double) for n in ("max_weight", "tol", "prec")] + \
+        [(n, ctypes.c_void_p) for n in ("n_q", "off", "key", "thr", "n_ent")]
+
+
+class LengthQueries(ctypes.Structure):
+    """sst_length_queries (include/sst.h): the queries both length-bound engines share."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("su", "obs", "spec", "alpha")] + \
+        [("n", ctypes.c_int64), ("tol", ctypes.c_double), ("prec", ctypes.c_double), ("max_len", ctypes.c_int),
+         ("max_mods", ctypes.c_int64)] + \
+        [(n, ctypes.c_void_p) for n in ("lower", "upper", "status", "qlen", "caps_len", "a0_len", "nodes")]
+
+
 class PostArgs(ctypes.Structure):
     """sst_post_args (include/sst.h): build_skeleton's fragments and the skeleton-based reduction."""
     _fields_ = [("n_spec", ctypes.c_int64), ("peak_off", ctypes.c_void_p), ("rows", ctypes.c_void_p),
@@ -308,19 +351,19 @@ def load_library(path=LIB_PATH):
     lib.sst_step_rows_device.restype = _I
     lib.sst_result_queries.argtypes = [_P, ctypes.POINTER(_I64)]
     lib.sst_result_queries.restype = _I
-    lib.sst_classify_rows_device.argtypes = [_P, _P, _P, _I64, _I64, _P, _D, _D, _P, _P, _P, _I, _D, _D, _D, _P, _P,
-                                             _P, _P, _P, _P, _P]
-    lib.sst_classify_rows_device.restype = _I
-    lib.sst_fix_round_device.argtypes = [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _D, _D, _D, _P,
-                                         ctypes.POINTER(ExactIO)]
-    lib.sst_fix_round_device.restype = _I
-    lib.sst_valid_rows_alpha_device.argtypes = [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _D, _D, _P]
-    lib.sst_valid_rows_alpha_device.restype = _I
-    lib.sst_bins_count_device.argtypes = [_P, _P, _I64, _P, _P, _P, _P, _P, _D, _P, _P, _P, _P]
-    lib.sst_bins_count_device.restype = _I
-    lib.sst_bins_emit_device.argtypes = [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _D, _D, _P, _P, _P, _P, _P, _P, _P,
-                                         _P, _P, _P]
-    lib.sst_bins_emit_device.restype = _I
+    # the row stages: (table, rows, the stage's struct, d_err[, exact-mode lists])
+    rows_p, exact_p = ctypes.POINTER(RowSlots), ctypes.POINTER(ExactIO)
+    for names, args, exact in ((("sst_classify_rows_device",), ClassifyArgs, False),
+                               (("sst_fix_round_device", "sst_fix_finish_device"), FixArgs, True),
+                               (("sst_bins_count_device", "sst_bins_emit_device"), BinsArgs, False),
+                               (("sst_dict_count_device",), DictArgs, False),
+                               (("sst_dict_build_device", "sst_dict_list_device"), DictArgs, True)):
+        for name in names:  # (restype: ctypes' default, int)
+            getattr(lib, name).argtypes = [_P, rows_p, ctypes.POINTER(args), _P] + ([exact_p] if exact else [])
+    lib.sst_valid_rows_alpha_device.argtypes = [_P, rows_p, _P, _P, _D, _D, _P]
+    lq_p = ctypes.POINTER(LengthQueries)
+    lib.sst_length_bounds_reach_device.argtypes = [_P, lq_p, _P, _P, _P, _I64, ctypes.c_uint32, _I]
+    lib.sst_length_bounds_frontier_device.argtypes = [_P, lq_p, _P, _P, _U64, ctypes.POINTER(LbfStats)]
     lib.sst_pyset_table_size.argtypes = [ctypes.c_uint32]
     lib.sst_pyset_table_size.restype = ctypes.c_uint32
     lib.sst_walk_scratch_bytes.argtypes = [ctypes.c_uint32] * 5
@@ -329,27 +372,12 @@ def load_library(path=LIB_PATH):
     lib.sst_skel_walk_device.restype = _I
     lib.sst_result_refs_device.argtypes = [_P, _P, _P, _P, _P]
     lib.sst_result_refs_device.restype = _I
-    lib.sst_dict_count_device.argtypes = [_P, _P, _I64, _P, _P, _P, _P, _P, _D, _D, _P, _P, _P]
-    lib.sst_dict_count_device.restype = _I
-    lib.sst_dict_build_device.argtypes = [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _D, _D, _D, _P, _P, _P, _P, _P,
-                                          ctypes.POINTER(ExactIO)]
-    lib.sst_dict_list_device.argtypes = [_P, _P, _I64, _P, _P, _P, _P, _P, _D, _D, _P, ctypes.POINTER(ExactIO)]
-    lib.sst_dict_list_device.restype = _I
-    lib.sst_fix_finish_device.argtypes = [_P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.POINTER(ExactIO)]
     lib.sst_pipe_reserve_rows.argtypes = [_P, _I64]
     lib.sst_pipe_reserve_rows.restype = _I
-    lib.sst_fix_finish_device.restype = _I
-    lib.sst_dict_build_device.restype = _I
     lib.sst_reach_rows_device.argtypes = [_P, _P, _P, _P, _I64, _P]
     lib.sst_reach_rows_device.restype = _I
-    lib.sst_length_bounds_reach_device.argtypes = [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _D, _D, _I, _I64, _P, _P, _P,
-                                                   _P, _P, _P, _P, _I64, ctypes.c_uint32, _I]
-    lib.sst_length_bounds_reach_device.restype = _I
     lib.sst_reach_lowest_device.argtypes = [_P, _P, _P, _P, _I64, _P, _P, _P]
     lib.sst_reach_lowest_device.restype = _I
-    lib.sst_length_bounds_frontier_device.argtypes = [_P, _P, _P, _P, _P, _P, _P, _I64, _D, _D, _I, _I64, _P, _P,
-                                                      _P, _P, _P, _P, _P, _U64, ctypes.POINTER(LbfStats)]
-    lib.sst_length_bounds_frontier_device.restype = _I
     lib.sst_post_skeleton_device.argtypes = [_P, ctypes.POINTER(PostArgs)]
     lib.sst_post_skeleton_device.restype = _I
     lib.sst_requery_merge_device.argtypes = [_P, ctypes.POINTER(RequeryMergeArgs), _P, _P]

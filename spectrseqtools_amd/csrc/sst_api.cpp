@@ -2273,38 +2273,53 @@ int sst_is_valid_alpha_device(sst_table* t, const double* d_mass, const double* 
 }
 
 // ---- config 5 on the device (sst_pipe.hip) ---------------------------
-static int pipe_args(sst_table* t, const double* d_obs, const int64_t* d_peak_off, int64_t n_spec, int64_t n_peaks,
-                     const double* d_intensity, double intensity_cutoff, double mass_cutoff, const double* d_su_seq,
-                     const double* shifts, const uint8_t* sides, int n_shifts, double max_weight, double tol,
-                     double prec, PipeArgs& a) {
-  if (!t || n_spec < 0 || n_spec > INT32_MAX || n_peaks < 0 || n_shifts < 1 || n_shifts > 4 || !shifts || !sides ||
-      (n_spec > 0 && (!d_obs || !d_peak_off || !d_su_seq)))
+// the arrays of an sst_row_slots a stage requires
+enum : unsigned { kRowOff = 1, kRowSu = 2, kRowObs = 4, kRowMeta = 8, kRowAlive = 16, kRowCnt = 32, kRowAll = 63 };
+
+static bool rows_missing(const sst_row_slots* r, unsigned need) {
+  return ((need & kRowOff) && !r->peak_off) || ((need & kRowSu) && !r->su) || ((need & kRowObs) && !r->obs) ||
+         ((need & kRowMeta) && !r->meta) || ((need & kRowAlive) && !r->alive) || ((need & kRowCnt) && !r->cnt);
+}
+
+// A row stage's table, row slots and own struct x: SST_E_ARG for a null one, an
+// n_spec out of range or (n_spec > 0) a required array that is null.
+static int check_rows(const sst_table* t, const sst_row_slots* r, const void* x, unsigned need) {
+  if (!t || !r || !x || r->n_spec < 0 || r->n_spec > INT32_MAX || (r->n_spec > 0 && rows_missing(r, need)))
     return SST_E_ARG;
+  return SST_OK;
+}
+
+// check_rows, then the row slots into a fresh PipeArgs
+static int row_slots(const sst_table* t, const sst_row_slots* r, const void* x, unsigned need, PipeArgs& a) {
+  if (int rc = check_rows(t, r, x, need)) return rc;
+  a = PipeArgs{};
+  a.peak_off = r->peak_off;
+  a.n_spec = r->n_spec;
+  a.r_su = r->su;
+  a.r_ob = r->obs;
+  a.r_meta = r->meta;
+  a.alive = r->alive;
+  a.cnt = r->cnt;
+  return SST_OK;
+}
+
+// the table's canonical rows (never dropped)
+static void canon_rows(const sst_table* t, PipeArgs& a) {
+  for (int r = 1; r < t->n_rows; ++r)
+    if (!t->is_mod[r]) a.canon[r >> 6] |= 1ull << (r & 63);
+}
+
+// classify's and the rounds' windows stay in the pair class; their tolerances and the canonical rows
+static int pair_class_args(sst_table* t, double max_weight, double mass_cutoff, double tol, double prec, PipeArgs& a) {
   if (!t->args.pairs_enabled) return fail(t->ctx, SST_E_ARG, "pipeline: the table has no pair list");
   const double hi_max = (max_weight + tol * 2.0 * mass_cutoff) / prec + 2.0;
   if (!(hi_max < (double)t->args.pair_hi))
     return fail(t->ctx, SST_E_ARG, "pipeline: windows may leave the pair class (max_weight / mass_cutoff too large)");
-  a = PipeArgs{};
-  a.obs = d_obs;
-  a.peak_off = d_peak_off;
-  a.n_spec = n_spec;
-  a.n_peaks = n_peaks;
-  a.intensity = d_intensity;
-  a.intensity_cutoff = intensity_cutoff;
-  a.mass_cutoff = mass_cutoff;
-  a.max_variance = 1.0;  // fragment_classification.py:8
-  a.su_seq = d_su_seq;
-  for (int k = 0; k < n_shifts; ++k) {
-    a.shift[k] = shifts[k];
-    a.sides[k] = sides[k];
-  }
-  a.n_shifts = n_shifts;
   a.max_weight = max_weight;
   a.tol = tol;
   a.prec = prec;
   a.rprec = 1.0 / prec;
-  for (int r = 1; r < t->n_rows; ++r)
-    if (!t->is_mod[r]) a.canon[r >> 6] |= 1ull << (r & 63);
+  canon_rows(t, a);
   return SST_OK;
 }
 
@@ -2319,33 +2334,48 @@ static void big_args(sst_ctx* c, sst::PipeArgs& a) {
   a.big_wg = c->pipe_big_wg;
 }
 
-int sst_classify_rows_device(sst_table* t, const double* d_obs, const int64_t* d_peak_off, int64_t n_spec,
-                             int64_t n_peaks, const double* d_intensity, double intensity_cutoff, double mass_cutoff,
-                             const double* d_su_seq, const double* shifts, const uint8_t* sides, int n_shifts,
-                             double max_weight, double tol, double prec, int8_t* d_valid_out, double* d_rows_su,
-                             double* d_rows_ob, uint32_t* d_rows_meta, uint8_t* d_alive, uint32_t* d_rows,
-                             uint32_t* d_err) {
+// A row stage's prologue, after its argument checks: the ctx lock (held while
+// this lives), the device, the alphabet masks' row limit (masks) and the
+// big-spectrum slices (a).  rc != 0: the stage returns it.
+struct StageScope {
+  std::lock_guard<std::recursive_mutex> g;
+  int rc;
+  StageScope(sst_table* t, bool masks, sst::PipeArgs* a = nullptr) : g(t->ctx->mu), rc(set_device(t->ctx)) {
+    if (!rc && masks) rc = check_masks(t);
+    if (!rc && a) big_args(t->ctx, *a);
+  }
+};
+
+int sst_classify_rows_device(sst_table* t, const sst_row_slots* rows, const sst_classify_args* x, uint32_t* d_err) {
   PipeArgs a;
-  if (int rc = pipe_args(t, d_obs, d_peak_off, n_spec, n_peaks, d_intensity, intensity_cutoff, mass_cutoff, d_su_seq,
-                         shifts, sides, n_shifts, max_weight, tol, prec, a))
-    return rc;
-  if (n_spec > 0 && (!d_rows_su || !d_rows_ob || !d_rows_meta || !d_alive || !d_rows || !d_err)) return SST_E_ARG;
+  if (int rc = row_slots(t, rows, x, kRowOff, a)) return rc;
+  if (x->n_peaks < 0 || x->n_shifts < 1 || x->n_shifts > 4 || !x->shifts || !x->sides ||
+      (a.n_spec > 0 && (!x->obs || !x->su_seq)))
+    return SST_E_ARG;
+  if (int rc = pair_class_args(t, x->max_weight, x->mass_cutoff, x->tol, x->prec, a)) return rc;
+  if (a.n_spec > 0 && (rows_missing(rows, kRowAll) || !d_err)) return SST_E_ARG;
+  a.obs = x->obs;
+  a.n_peaks = x->n_peaks;
+  a.intensity = x->intensity;
+  a.intensity_cutoff = x->intensity_cutoff;
+  a.mass_cutoff = x->mass_cutoff;
+  a.max_variance = 1.0;  // fragment_classification.py:8
+  a.su_seq = x->su_seq;
+  for (int k = 0; k < x->n_shifts; ++k) {
+    a.shift[k] = x->shifts[k];
+    a.sides[k] = x->sides[k];
+  }
+  a.n_shifts = x->n_shifts;
+  a.valid_out = x->valid_out;
+  a.err = d_err;
   sst_ctx* c = t->ctx;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  if (int rc = set_device(c)) return rc;
+  StageScope s(t, false, &a);  // spectra of more than kPipeMaxPeaks peaks: k_classify_rows_big in the reserved slices
+  if (s.rc) return s.rc;
   if (!c->singleton_masses.ensure((size_t)t->n_rows * 8)) return fail(c, SST_E_NOMEM, "device allocation failed");
   HIP_OK(c, hipMemcpyAsync(c->singleton_masses.p, t->masses.data(), (size_t)t->n_rows * 8, hipMemcpyHostToDevice,
                            c->stream));
   a.masses = (const int64_t*)c->singleton_masses.p;
   a.n_masses = t->n_rows;
-  a.valid_out = d_valid_out;
-  a.r_su = d_rows_su;
-  a.r_ob = d_rows_ob;
-  a.r_meta = d_rows_meta;
-  a.alive = d_alive;
-  a.cnt = d_rows;
-  a.err = d_err;
-  big_args(c, a);  // spectra of more than kPipeMaxPeaks peaks: k_classify_rows_big in the reserved slices
   Prof p(c, SST_K_CLASSIFY_ROWS);
   HIP_OK(c, launch_classify_rows(t->args, a, c->n_cu, c->stream));
   return SST_OK;
@@ -2403,138 +2433,100 @@ int sst_pipe_reserve_rows(sst_table* t, int64_t max_rows) {
   return SST_OK;
 }
 
-int sst_fix_round_device(sst_table* t, const int64_t* d_peak_off, int64_t n_spec, const double* d_rows_su,
-                         const double* d_rows_ob, const uint32_t* d_rows_meta, uint8_t* d_alive,
-                         const uint32_t* d_rows, const uint64_t* d_alpha, uint64_t* d_alpha_next,
-                         const uint8_t* d_active, uint8_t* d_active_next, uint32_t* d_rounds, uint32_t* d_queries,
-                         uint32_t* d_n_active, double max_weight, double tol, double prec, uint32_t* d_err,
-                         const sst_exact_io* x) {
-  const double zero_shift = 0.0;
-  const uint8_t zero_side = 0;
-  PipeArgs a;
-  if (int rc = pipe_args(t, d_rows_su, d_peak_off, n_spec, 0, nullptr, 0.0, 0.0, d_rows_su, &zero_shift,
-                         &zero_side, 1, max_weight, tol, prec, a))
-    return rc;
-  if (n_spec > 0 && (!d_rows_ob || !d_rows_meta || !d_alive || !d_rows || !d_alpha || !d_alpha_next || !d_active ||
-                     !d_active_next || !d_rounds || !d_queries || !d_n_active || !d_err))
-    return SST_E_ARG;
-  sst_ctx* c = t->ctx;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  if (int rc = set_device(c)) return rc;
-  if (int rc = check_masks(t)) return rc;
-  a.r_su = const_cast<double*>(d_rows_su);
-  a.r_ob = const_cast<double*>(d_rows_ob);
-  a.r_meta = const_cast<uint32_t*>(d_rows_meta);
-  a.alive = d_alive;
-  a.cnt = const_cast<uint32_t*>(d_rows);
-  a.alpha = d_alpha;
-  a.alpha_next = d_alpha_next;
-  a.active = d_active;
-  a.active_next = d_active_next;
-  a.rounds = d_rounds;
-  a.queries = d_queries;
-  a.n_active = d_n_active;
+// the round's own arrays (sst_fix_args) into the stage's arguments; false: one is null
+static bool fix_args(const sst_fix_args* f, uint32_t* d_err, PipeArgs& a) {
+  a.alpha = f->alpha;
+  a.alpha_next = f->alpha_next;
+  a.active = f->active;
+  a.active_next = f->active_next;
+  a.rounds = f->rounds;
+  a.queries = f->queries;
+  a.n_active = f->n_active;
   a.err = d_err;
+  return f->alpha && f->alpha_next && f->active && f->active_next && f->rounds && f->queries && f->n_active && d_err;
+}
+
+int sst_fix_round_device(sst_table* t, const sst_row_slots* rows, const sst_fix_args* f, uint32_t* d_err,
+                         const sst_exact_io* x) {
+  PipeArgs a;
+  if (int rc = row_slots(t, rows, f, kRowOff | kRowSu, a)) return rc;
+  if (int rc = pair_class_args(t, f->max_weight, 0.0, f->tol, f->prec, a)) return rc;
+  if ((!fix_args(f, d_err, a) || rows_missing(rows, kRowAll)) && a.n_spec > 0) return SST_E_ARG;
+  sst_ctx* c = t->ctx;
+  StageScope s(t, true, &a);
+  if (s.rc) return s.rc;
   if (int rc = exact_io(c, x, a)) return rc;
-  if (n_spec > 0) HIP_OK(c, hipMemsetAsync(d_n_active, 0, sizeof(uint32_t), c->stream));  // this round's count
-  big_args(c, a);
+  if (a.n_spec > 0) HIP_OK(c, hipMemsetAsync(a.n_active, 0, sizeof(uint32_t), c->stream));  // this round's count
   Prof p(c, SST_K_FIX_ROUND);
   HIP_OK(c, launch_fix_round(t->args, a, c->n_cu, c->stream));
   return SST_OK;
 }
 
-static int bins_args(sst_table* t, const int64_t* d_peak_off, int64_t n_spec, const double* d_rows_su,
-                     const double* d_rows_ob, const uint32_t* d_rows_meta, const uint8_t* d_alive,
-                     const uint32_t* d_rows, double tol, double prec, uint64_t* d_q_off, uint32_t* d_err, PipeArgs& a) {
-  if (!t || n_spec < 0 || n_spec > INT32_MAX || !d_q_off ||
-      (n_spec > 0 && (!d_peak_off || !d_rows_su || !d_rows_ob || !d_rows_meta || !d_alive || !d_rows || !d_err)))
-    return SST_E_ARG;
+// both bins passes: every row array, q_off and d_err (the count pass rounds no window: precision 1)
+static int bins_rows(sst_table* t, const sst_row_slots* rows, const sst_bins_args* b, uint32_t* d_err, bool emit,
+                     PipeArgs& a) {
+  if (int rc = row_slots(t, rows, b, kRowAll, a)) return rc;
+  if (!b->q_off || (a.n_spec > 0 && !d_err)) return SST_E_ARG;
   if (!t->args.pairs_enabled) return fail(t->ctx, SST_E_ARG, "skeleton bins: the table has no pair list");
-  a = PipeArgs{};
-  a.peak_off = d_peak_off;
-  a.n_spec = n_spec;
-  a.r_su = const_cast<double*>(d_rows_su);
-  a.r_ob = const_cast<double*>(d_rows_ob);
-  a.r_meta = const_cast<uint32_t*>(d_rows_meta);
-  a.alive = const_cast<uint8_t*>(d_alive);
-  a.cnt = const_cast<uint32_t*>(d_rows);
-  a.tol = tol;
-  a.prec = prec;
-  a.rprec = 1.0 / prec;
-  a.q_off = d_q_off;
+  a.tol = b->tol;
+  a.prec = emit ? b->prec : 1.0;
+  a.rprec = 1.0 / a.prec;
+  a.q_off = b->q_off;
   a.err = d_err;
   return SST_OK;
 }
 
-int sst_bins_count_device(sst_table* t, const int64_t* d_peak_off, int64_t n_spec, const double* d_rows_su,
-                          const double* d_rows_ob, const uint32_t* d_rows_meta, const uint8_t* d_alive,
-                          const uint32_t* d_rows, double tol, uint32_t* d_n_q, uint64_t* d_q_off, uint32_t* d_err,
-                          uint32_t* d_n_q0) {
+int sst_bins_count_device(sst_table* t, const sst_row_slots* rows, const sst_bins_args* b, uint32_t* d_err) {
   PipeArgs a;
-  if (int rc = bins_args(t, d_peak_off, n_spec, d_rows_su, d_rows_ob, d_rows_meta, d_alive, d_rows, tol, 1.0,
-                         d_q_off, d_err, a))
-    return rc;
-  if (n_spec > 0 && !d_n_q) return SST_E_ARG;
-  a.n_q = d_n_q;
-  a.n_q0 = d_n_q0;
+  if (int rc = bins_rows(t, rows, b, d_err, false, a)) return rc;
+  if (a.n_spec > 0 && !b->n_q) return SST_E_ARG;
+  a.n_q = b->n_q;
+  a.n_q0 = b->n_q0;
   sst_ctx* c = t->ctx;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  if (int rc = set_device(c)) return rc;
-  big_args(c, a);
+  StageScope s(t, false, &a);
+  if (s.rc) return s.rc;
   Prof p(c, SST_K_BINS_COUNT);
   HIP_OK(c, launch_bins_count(a, c->n_cu, c->stream));
   return SST_OK;
 }
 
-int sst_bins_emit_device(sst_table* t, const int64_t* d_peak_off, int64_t n_spec, const double* d_rows_su,
-                         const double* d_rows_ob, const uint32_t* d_rows_meta, const uint8_t* d_alive,
-                         const uint32_t* d_rows, const uint64_t* d_alpha, double tol, double prec,
-                         const uint64_t* d_q_off, int8_t* d_status, uint32_t* d_count, double* d_def_mass,
-                         double* d_def_thr, int32_t* d_def_spec, uint64_t* d_def_q, uint32_t* d_n_def,
-                         uint32_t* d_err, const uint8_t* d_pair_ok) {
+int sst_bins_emit_device(sst_table* t, const sst_row_slots* rows, const sst_bins_args* b, uint32_t* d_err) {
   PipeArgs a;
-  if (int rc = bins_args(t, d_peak_off, n_spec, d_rows_su, d_rows_ob, d_rows_meta, d_alive, d_rows, tol, prec,
-                         const_cast<uint64_t*>(d_q_off), d_err, a))
-    return rc;
-  if (n_spec > 0 && (!d_alpha || !d_status || !d_count)) return SST_E_ARG;
-  a.alpha = d_alpha;
-  a.q_status = d_status;
-  a.q_count = d_count;
-  if (d_n_def && (!d_def_mass || !d_def_thr || !d_def_spec || !d_def_q)) return SST_E_ARG;
-  a.def_mass = d_def_mass;
-  a.def_thr = d_def_thr;
-  a.def_spec = d_def_spec;
-  a.def_q = d_def_q;
-  a.n_def = d_n_def;
-  a.pair_ok = d_pair_ok;
+  if (int rc = bins_rows(t, rows, b, d_err, true, a)) return rc;
+  if (a.n_spec > 0 && (!b->alpha || !b->status || !b->count)) return SST_E_ARG;
+  a.alpha = b->alpha;
+  a.q_status = b->status;
+  a.q_count = b->count;
+  if (b->n_def && (!b->def_mass || !b->def_thr || !b->def_spec || !b->def_q)) return SST_E_ARG;
+  a.def_mass = b->def_mass;
+  a.def_thr = b->def_thr;
+  a.def_spec = b->def_spec;
+  a.def_q = b->def_q;
+  a.n_def = b->n_def;
+  a.pair_ok = b->pair_ok;
   sst_ctx* c = t->ctx;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  if (int rc = set_device(c)) return rc;
-  if (int rc = check_masks(t)) return rc;
-  big_args(c, a);
+  StageScope s(t, true, &a);
+  if (s.rc) return s.rc;
   Prof p(c, SST_K_BINS_EMIT);
   HIP_OK(c, launch_bins_emit(t->args, a, c->n_cu, c->stream));
   return SST_OK;
 }
 
-int sst_valid_rows_alpha_device(sst_table* t, const int64_t* d_peak_off, int64_t n_spec, const double* d_rows_su,
-                                const double* d_rows_ob, const uint32_t* d_rows, const uint64_t* d_alpha,
-                                const uint8_t* d_active, uint8_t* d_alive, double tol, double prec, uint32_t* d_err) {
-  if (!t || n_spec < 0 || n_spec > INT32_MAX ||
-      (n_spec > 0 && (!d_peak_off || !d_rows_su || !d_rows_ob || !d_rows || !d_alpha || !d_alive || !d_err)))
-    return SST_E_ARG;
+int sst_valid_rows_alpha_device(sst_table* t, const sst_row_slots* rows, const uint64_t* d_alpha,
+                                const uint8_t* d_active, double tol, double prec, uint32_t* d_err) {
+  if (int rc = check_rows(t, rows, rows, kRowAll & ~kRowMeta)) return rc;
+  if (rows->n_spec > 0 && (!d_alpha || !d_err)) return SST_E_ARG;
   sst_ctx* c = t->ctx;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  if (int rc = set_device(c)) return rc;
-  if (int rc = check_masks(t)) return rc;
+  StageScope s(t, true);
+  if (s.rc) return s.rc;
   AlphaArgs a{};
-  a.mass = d_rows_su;
-  a.thr_obs = d_rows_ob;  // the rows' thresholds: tolerance * observed mass (prediction.py:219)
-  a.offsets = d_peak_off;
-  a.counts = d_rows;
+  a.mass = rows->su;
+  a.thr_obs = rows->obs;  // the rows' thresholds: tolerance * observed mass (prediction.py:219)
+  a.offsets = rows->peak_off;
+  a.counts = rows->cnt;
   a.masks = d_alpha;
   a.active = d_active;
-  a.alive = d_alive;
+  a.alive = rows->alive;
   a.err = d_err;
   a.w = t->args.w;
   a.n_rows = t->n_rows;
@@ -2543,7 +2535,7 @@ int sst_valid_rows_alpha_device(sst_table* t, const int64_t* d_peak_off, int64_t
   a.rprec = 1.0 / prec;
   if (int rc = canon_closure(t, a)) return rc;
   Prof p(c, SST_K_VALID_ALPHA);
-  HIP_OK(c, launch_valid_alpha(a, n_spec, c->stream));
+  HIP_OK(c, launch_valid_alpha(a, rows->n_spec, c->stream));
   return SST_OK;
 }
 
@@ -2574,241 +2566,6 @@ int sst_is_valid_alpha(sst_table* t, const double* mass, const double* thr, cons
   HIP_OK(c, hipMemcpyAsync(out, dout, n, hipMemcpyDeviceToHost, c->stream));
   HIP_OK(c, hipStreamSynchronize(c->stream));
   return SST_OK;
-}
-
-}  // extern "C"
-static int lbf_frontier(sst_table* t, sst_ctx::LbfWs& W, const double* d_su, const double* d_obs,
-                        const int32_t* d_spec, const uint64_t* d_alpha, const uint8_t* d_lr, const uint64_t* d_lr_off,
-                        int64_t n, double tol, double prec, int max_len, int64_t max_mods, int64_t* d_lower,
-                        int64_t* d_upper, int8_t* d_status, const int32_t* d_qlen, const int32_t* d_caps_len,
-                        const int32_t* d_a0_len, uint64_t* d_nodes, uint64_t workspace_bytes, sst_lbf_stats* stats);
-namespace {
-constexpr uint64_t kBatchFrontierBytes = 4ull << 30;  // sst_length_bound_batch's frontier workspace
-
-static int length_bound_batch(sst_table* t, const double* su, const double* obs, int64_t n, double tol, double prec,
-                              int max_len, int64_t max_mods, int direction, int64_t* out, int8_t* status,
-                              const int32_t* spec, const uint64_t* alpha, int64_t n_alpha) {
-  const bool exact_only = (direction & SST_LB_EXACT_ONLY) != 0;
-  const bool replay_only = (direction & SST_LB_REPLAY) != 0;
-  direction &= ~(SST_LB_EXACT_ONLY | SST_LB_REPLAY);
-  if (!t || n < 0 || n > INT32_MAX || (n > 0 && (!su || !obs || !out || !status)) || (direction != 0 && direction != 1) ||
-      max_len < 0 || max_len > 253)
-    return SST_E_ARG;
-  sst_ctx* c = t->ctx;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  if (int rc = set_device(c)) return rc;
-  if (n == 0) return SST_OK;
-  const size_t nn = (size_t)n;
-  DevBuf d_su, d_obs, d_out, d_st, d_list, d_cnt, layers, d_spec, d_alpha;
-  if (!d_su.ensure(nn * 8) || !d_obs.ensure(nn * 8) || !d_out.ensure(nn * 8) || !d_st.ensure(nn) ||
-      !d_list.ensure(nn * 4) || !d_cnt.ensure(4))
-    return fail(c, SST_E_NOMEM, "device allocation failed (length bound)");
-  if (alpha) {
-    for (int64_t i = 0; spec && i < n; ++i)
-      if (spec[i] < 0 || spec[i] >= n_alpha) return fail(c, SST_E_ARG, "length bound: alphabet index out of range");
-    if (!d_alpha.ensure((size_t)n_alpha * 16) || (spec && !d_spec.ensure(nn * 4)))
-      return fail(c, SST_E_NOMEM, "device allocation failed (length bound alphabets)");
-    HIP_OK(c, hipMemcpyAsync(d_alpha.p, alpha, (size_t)n_alpha * 16, hipMemcpyHostToDevice, c->stream));
-    if (spec) HIP_OK(c, hipMemcpyAsync(d_spec.p, spec, nn * 4, hipMemcpyHostToDevice, c->stream));
-  }
-  HIP_OK(c, hipMemcpyAsync(d_su.p, su, nn * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_OK(c, hipMemcpyAsync(d_obs.p, obs, nn * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_OK(c, hipMemsetAsync(d_cnt.p, 0, 4, c->stream));
-  LBArgs q{};
-  q.su = (const double*)d_su.p;
-  q.obs = (const double*)d_obs.p;
-  q.n = n;
-  q.tol = tol;
-  q.prec = prec;
-  q.rprec = 1.0 / prec;
-  q.A0 = (int)std::max<int64_t>(0, std::min<int64_t>(max_mods, kInfBudget));  // round(rate * max_len) >= 0
-  q.dir = direction;
-  q.max_len = max_len;
-  q.out = (int64_t*)d_out.p;
-  q.status = (int8_t*)d_st.p;
-  q.exact_list = (uint32_t*)d_list.p;
-  q.exact_count = (uint32_t*)d_cnt.p;
-  q.node_budget = kLBNodeBudget;
-  q.alpha = alpha ? (const uint64_t*)d_alpha.p : nullptr;
-  q.spec = alpha && spec ? (const int32_t*)d_spec.p : nullptr;
-  q.comp = (int)t->C;
-  // fast path: layered reachability up to the largest window (a host-side
-  // over-estimate; the kernel re-checks hi < layer_limit exactly), kept below
-  // the reference's masked last column
-  if (t->closure && t->args.w_min > 0 && !exact_only && !alpha) {
-    double hmax = 0;
-    for (int64_t i = 0; i < n; ++i) hmax = std::max(hmax, (su[i] + tol * std::fabs(obs[i])) / prec + 4.0);
-    const int64_t safe = (t->n_cols - 1) * t->C;
-    const int64_t lim = std::min<int64_t>(safe, (int64_t)std::min(hmax, (double)safe));
-    if (lim > 0) {
-      const int64_t words = (lim + 63) / 64;
-      const int n_layers = (int)(lim / t->args.w_min) + 2;
-      if (!layers.ensure((size_t)n_layers * words * 8)) return fail(c, SST_E_NOMEM, "device allocation failed (layers)");
-      uint64_t* L = (uint64_t*)layers.p;
-      const uint64_t one = 1;
-      HIP_OK(c, hipMemsetAsync(L, 0, (size_t)words * 8, c->stream));
-      HIP_OK(c, hipMemcpyAsync(L, &one, 8, hipMemcpyHostToDevice, c->stream));
-      for (int k = 0; k + 1 < n_layers; ++k)
-        HIP_OK(c, launch_layer_step(L + (size_t)k * words, L + (size_t)(k + 1) * words, words, t->args.w, t->n_rows,
-                                    c->stream));
-      q.layers = L;
-      q.layer_words = words;
-      q.n_layers = n_layers;
-      q.layer_limit = lim;
-    }
-  }
-  // fast kernel (queues the rest), then the exact kernel; retried with a
-  // larger per-lane memo while any query reports hash exhaustion
-  uint32_t n_exact = 0;
-  {
-    Prof p(c, SST_K_LENGTH_BOUND);
-    HIP_OK(c, launch_length_bound(t->args, q, nullptr, nullptr, nullptr, 0, 0, true, c->stream));
-  }
-  HIP_OK(c, hipMemcpyAsync(&n_exact, d_cnt.p, 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_OK(c, hipStreamSynchronize(c->stream));
-  std::vector<int8_t> st(nn);
-  DevBuf f_alpha, f_words, f_off, f_bits, f_lr, f_lro, f_spec, f_lo, f_hi, f_st;
-  bool frontier_ok = t->closure && !alpha && !replay_only && t->args.w_min >= 1024;  // (the reach rows' LDS ring)
-  int64_t w_top = 0;
-  for (int r = 1; r < t->n_rows && frontier_ok; ++r) {
-    frontier_ok = t->masses[r] < (1 << 20);
-    w_top = std::max<int64_t>(w_top, t->masses[r]);
-  }
-  // the frontier applies the reduced-alphabet extent ceil((w_top * 35 + 1) / C) * C
-  // (mass_table.py:116): only a table of exactly that extent (every table built
-  // here, the reference's cache) is answered by it; an uploaded table of another
-  // extent goes to the replay, which reads the table's own
-  frontier_ok = frontier_ok && (w_top * 35 + t->C) / t->C == t->n_cols;
-  if (n_exact && frontier_ok) {
-    // the first-visit frontier (DESIGN §3) on the table's own rows, both
-    // directions, for the queries the fast path left pending only (its own
-    // answers stay); a window in the table's last packed word, where the
-    // frontier's reachability cannot see the last-column mask (SST_ABORTED
-    // there), or one the frontier's layout cannot hold, goes on to the replay
-    const size_t m = n_exact;
-    std::vector<uint32_t> pend(m);
-    HIP_OK(c, hipMemcpyAsync(pend.data(), d_list.p, m * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    std::vector<double> psu(m), pob(m);
-    int64_t hmax = 1;
-    for (size_t j = 0; j < m; ++j) {
-      psu[j] = su[pend[j]];
-      pob[j] = obs[pend[j]];
-      hmax = std::max<int64_t>(hmax, (int64_t)((psu[j] + tol * std::fabs(pob[j])) / prec) + 4);
-    }
-    hmax = std::min<int64_t>(hmax, t->n_cols * t->C);
-    const int64_t words = hmax / 32 + 2;
-    uint64_t am[2] = {0, 0};
-    for (int r = 1; r < t->n_rows; ++r) am[r >> 6] |= 1ull << (r & 63);
-    const int64_t zero = 0;
-    const size_t K = (size_t)(t->n_rows - 1);
-    DevBuf f_su, f_ob;
-    if (!f_alpha.ensure(16) || !f_words.ensure(8) || !f_off.ensure(8) || !f_bits.ensure(K * words * 4) ||
-        !f_lr.ensure((size_t)words * 32) || !f_lro.ensure(8) || !f_spec.ensure(m * 4) || !f_lo.ensure(m * 8) ||
-        !f_hi.ensure(m * 8) || !f_st.ensure(m) || !f_su.ensure(m * 8) || !f_ob.ensure(m * 8))
-      return fail(c, SST_E_NOMEM, "device allocation failed (length bound, frontier)");
-    HIP_OK(c, hipMemcpyAsync(f_alpha.p, am, 16, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(c, hipMemcpyAsync(f_words.p, &words, 8, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(c, hipMemcpyAsync(f_off.p, &zero, 8, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(c, hipMemcpyAsync(f_lro.p, &zero, 8, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(c, hipMemcpyAsync(f_su.p, psu.data(), m * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(c, hipMemcpyAsync(f_ob.p, pob.data(), m * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(c, hipMemsetAsync(f_spec.p, 0, m * 4, c->stream));
-    if (int rc = sst_reach_rows_device(t, (const uint64_t*)f_alpha.p, (const int64_t*)f_words.p,
-                                       (const uint64_t*)f_off.p, 1, (uint32_t*)f_bits.p))
-      return rc;
-    if (int rc = sst_reach_lowest_device(t, (const uint64_t*)f_alpha.p, (const int64_t*)f_words.p,
-                                         (const uint64_t*)f_off.p, 1, (const uint32_t*)f_bits.p,
-                                         (const uint64_t*)f_lro.p, (uint8_t*)f_lr.p))
-      return rc;
-    if (int rc = lbf_frontier(t, c->lbf_small, (const double*)f_su.p, (const double*)f_ob.p,
-                              (const int32_t*)f_spec.p, (const uint64_t*)f_alpha.p, (const uint8_t*)f_lr.p,
-                              (const uint64_t*)f_lro.p, (int64_t)m, tol, prec, max_len, max_mods, (int64_t*)f_lo.p,
-                              (int64_t*)f_hi.p, (int8_t*)f_st.p, nullptr, nullptr, nullptr, nullptr, kBatchFrontierBytes,
-                              nullptr))
-      return rc;
-    // scatter the frontier's answers over the fast pass's (host copies: nn x 9 bytes)
-    std::vector<int64_t> fv(m), ov(nn);
-    std::vector<int8_t> fs(m);
-    HIP_OK(c, hipMemcpyAsync(fv.data(), direction ? f_hi.p : f_lo.p, m * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipMemcpyAsync(fs.data(), f_st.p, m, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipMemcpyAsync(ov.data(), d_out.p, nn * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipMemcpyAsync(st.data(), d_st.p, nn, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    std::vector<uint32_t> rest;
-    for (size_t j = 0; j < m; ++j) {
-      ov[pend[j]] = fv[j];
-      st[pend[j]] = fs[j];
-      if (fs[j] == SST_ABORTED) rest.push_back(pend[j]);
-    }
-    HIP_OK(c, hipMemcpyAsync(d_out.p, ov.data(), nn * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(c, hipMemcpyAsync(d_st.p, st.data(), nn, hipMemcpyHostToDevice, c->stream));
-    n_exact = (uint32_t)rest.size();
-    if (n_exact) {
-      HIP_OK(c, hipMemcpyAsync(d_list.p, rest.data(), rest.size() * 4, hipMemcpyHostToDevice, c->stream));
-      HIP_OK(c, hipMemcpyAsync(d_cnt.p, &n_exact, 4, hipMemcpyHostToDevice, c->stream));
-    }
-    HIP_OK(c, hipStreamSynchronize(c->stream));  // the host vectors above are read by the copies
-  }
-  if (n_exact && max_len > 120)  // the frontier answers up to 253; the replay's int8 value slots hold 121
-    return fail(c, SST_E_ARG,
-                "length bound: max_len " + std::to_string(max_len) + " above 120 for a window only the DFS replay "
-                "answers (the table's last packed word, or beyond the frontier's layout)");
-  if (n_exact) {
-    // one 64-lane block per query in flight (k_length_exact<WAVE>), each with
-    // its own memo slice: up to 1 024 at once (4 waves per CU; the memo slices
-    // then take ~10 GB of HBM), batches of many spectra keep the chip busy
-    int units = (int)std::min<uint32_t>(1024, n_exact);
-    uint32_t cap = memo_cap0(units, kLBHashCap0);
-    for (;;) {
-      DevBuf hash, vals, frames;
-      if (!hash.ensure((size_t)units * cap * hash_entry_bytes()) || !vals.ensure((size_t)units * cap * kMaxRows) ||
-          !frames.ensure((size_t)units * lb_frame_bytes()))
-        return fail(c, SST_E_NOMEM, "device allocation failed (length-bound memo)");
-      HIP_OK(c, hipMemsetAsync(hash.p, 0, hash.bytes, c->stream));
-      Prof p(c, SST_K_LENGTH_BOUND);
-      HIP_OK(c, launch_length_bound(t->args, q, (char*)hash.p, (int8_t*)vals.p, (char*)frames.p, cap, units, false,
-                                    c->stream));
-      HIP_OK(c, hipMemcpyAsync(st.data(), d_st.p, nn, hipMemcpyDeviceToHost, c->stream));
-      HIP_OK(c, hipStreamSynchronize(c->stream));
-      bool retry = false;
-      for (size_t i = 0; i < nn; ++i) retry |= st[i] == kStatusExactRetry;
-      if (!retry) break;
-      if ((size_t)std::max(1, units / 8) * cap * 8 * (hash_entry_bytes() + kMaxRows) > kMaxMemoBytes)
-        return fail(c, SST_E_NOMEM, "length bound: memo would exceed the workspace limit");
-      cap *= 8;
-      units = std::max(1, units / 8);
-    }
-  }
-  HIP_OK(c, hipMemcpyAsync(out, d_out.p, nn * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_OK(c, hipMemcpyAsync(status, d_st.p, nn, hipMemcpyDeviceToHost, c->stream));
-  HIP_OK(c, hipStreamSynchronize(c->stream));
-  for (size_t i = 0; i < nn; ++i)
-    if (status[i] == kStatusPending || status[i] == kStatusExactRetry)
-      return fail(c, SST_E_INTERNAL, "length bound: query left unresolved (internal error)");
-  return SST_OK;
-}
-
-}  // namespace
-extern "C" {
-
-int sst_length_bound_batch(sst_table* t, const double* su, const double* obs, int64_t n, double tol, double prec,
-                           int max_len, int64_t max_mods, int direction, int64_t* out, int8_t* status) {
-  return length_bound_batch(t, su, obs, n, tol, prec, max_len, max_mods, direction, out, status, nullptr, nullptr,
-                            0);
-}
-
-int sst_length_bound_alpha_batch(sst_table* t, const double* su, const double* obs, const int32_t* spec,
-                                 const uint64_t* alpha, int64_t n_alpha, int64_t n, double tol, double prec,
-                                 int max_len, int64_t max_mods, int direction, int64_t* out, int8_t* status) {
-  // "lower" only: a left child that is reachable in the full table but not with
-  // the kept rows returns the default (-1) there, and the reference's upper
-  // bound counts such a visited child as -1 + 1 = 0 where the rebuilt table
-  // would not visit it at all (DESIGN §3); the lower bound's default (max_len
-  // + 1) can never win a min, so its masked replay is exact
-  if (!alpha || n_alpha <= 0 || (direction & ~SST_LB_EXACT_ONLY) != 0) return SST_E_ARG;
-  return length_bound_batch(t, su, obs, n, tol, prec, max_len, max_mods, direction, out, status, spec, alpha,
-                            n_alpha);
 }
 
 }  // extern "C"
@@ -3041,134 +2798,84 @@ extern "C" int64_t sst_pyset_order(const int32_t* keys, const int64_t* hashes, i
 }
 
 // ---- config 5: final dict, skeleton walk, candidate references -----------
-extern "C" int sst_dict_count_device(sst_table* t, const int64_t* d_peak_off, int64_t n_spec, const double* d_rows_su,
-                                     const double* d_rows_ob, const uint32_t* d_rows_meta, const uint8_t* d_alive,
-                                     const uint32_t* d_rows, double max_weight, double tol, uint32_t* d_n_q,
-                                     uint64_t* d_off, uint32_t* d_err) {
-  if (!t || n_spec < 0 || n_spec > INT32_MAX || !d_off ||
-      (n_spec > 0 && (!d_peak_off || !d_rows_su || !d_rows_ob || !d_rows_meta || !d_alive || !d_rows || !d_n_q ||
-                      !d_err)))
-    return SST_E_ARG;
-  sst_ctx* c = t->ctx;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  if (int rc = set_device(c)) return rc;
-  sst::PipeArgs a{};
-  a.peak_off = d_peak_off;
-  a.n_spec = n_spec;
-  a.r_su = const_cast<double*>(d_rows_su);
-  a.r_ob = const_cast<double*>(d_rows_ob);
-  a.r_meta = const_cast<uint32_t*>(d_rows_meta);
-  a.alive = const_cast<uint8_t*>(d_alive);
-  a.cnt = const_cast<uint32_t*>(d_rows);
-  a.max_weight = max_weight;
-  a.tol = tol;
+// the three dict passes: every row array and d_err; the dict's weight limit and tolerance
+static int dict_rows(sst_table* t, const sst_row_slots* rows, const sst_dict_args* d, uint32_t* d_err,
+                     sst::PipeArgs& a) {
+  if (int rc = row_slots(t, rows, d, kRowAll, a)) return rc;
+  if (a.n_spec > 0 && !d_err) return SST_E_ARG;
+  a.max_weight = d->max_weight;
+  a.tol = d->tol;
   a.err = d_err;
-  sst::DictArgs d{};
-  d.n_q = d_n_q;
-  big_args(c, a);
-  Prof p(c, SST_K_DICT);
-  HIP_OK(c, sst::launch_dict(t->args, a, d, 1, c->n_cu, c->stream));
-  HIP_OK(c, sst::launch_scan_u32(d_n_q, d_off, n_spec, c->stream));
   return SST_OK;
 }
 
-extern "C" int sst_dict_build_device(sst_table* t, const int64_t* d_peak_off, int64_t n_spec, const double* d_rows_su,
-                                     const double* d_rows_ob, const uint32_t* d_rows_meta, const uint8_t* d_alive,
-                                     const uint32_t* d_rows, const uint64_t* d_alpha, double max_weight, double tol,
-                                     double prec, const uint64_t* d_off, uint64_t* d_key, double* d_thr,
-                                     uint32_t* d_n_ent, uint32_t* d_err, const sst_exact_io* x) {
-  if (!t || n_spec < 0 || n_spec > INT32_MAX ||
-      (n_spec > 0 && (!d_peak_off || !d_rows_su || !d_rows_ob || !d_rows_meta || !d_alive || !d_rows || !d_alpha ||
-                      !d_off || !d_n_ent || !d_err)))
-    return SST_E_ARG;
+extern "C" int sst_dict_count_device(sst_table* t, const sst_row_slots* rows, const sst_dict_args* x,
+                                     uint32_t* d_err) {
+  sst::PipeArgs a;
+  if (int rc = dict_rows(t, rows, x, d_err, a)) return rc;
+  if (!x->off || (a.n_spec > 0 && !x->n_q)) return SST_E_ARG;
+  sst_ctx* c = t->ctx;
+  StageScope s(t, false, &a);
+  if (s.rc) return s.rc;
+  sst::DictArgs d{};
+  d.n_q = x->n_q;
+  Prof p(c, SST_K_DICT);
+  HIP_OK(c, sst::launch_dict(t->args, a, d, 1, c->n_cu, c->stream));
+  HIP_OK(c, sst::launch_scan_u32(x->n_q, x->off, a.n_spec, c->stream));
+  return SST_OK;
+}
+
+extern "C" int sst_dict_build_device(sst_table* t, const sst_row_slots* rows, const sst_dict_args* x,
+                                     uint32_t* d_err, const sst_exact_io* xio) {
+  sst::PipeArgs a;
+  if (int rc = dict_rows(t, rows, x, d_err, a)) return rc;
+  if (a.n_spec > 0 && (!x->alpha || !x->off || !x->n_ent)) return SST_E_ARG;
   if (!t->args.pairs_enabled) return fail(t->ctx, SST_E_ARG, "final dict: the table has no pair list");
   sst_ctx* c = t->ctx;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  if (int rc = set_device(c)) return rc;
-  if (int rc = check_masks(t)) return rc;
-  sst::PipeArgs a{};
-  a.peak_off = d_peak_off;
-  a.n_spec = n_spec;
-  a.r_su = const_cast<double*>(d_rows_su);
-  a.r_ob = const_cast<double*>(d_rows_ob);
-  a.r_meta = const_cast<uint32_t*>(d_rows_meta);
-  a.alive = const_cast<uint8_t*>(d_alive);
-  a.cnt = const_cast<uint32_t*>(d_rows);
-  a.alpha = d_alpha;
-  a.max_weight = max_weight;
-  a.tol = tol;
-  a.prec = prec;
-  a.rprec = 1.0 / prec;
-  a.err = d_err;
+  StageScope s(t, true, &a);
+  if (s.rc) return s.rc;
+  a.alpha = x->alpha;
+  a.prec = x->prec;
+  a.rprec = 1.0 / x->prec;
   sst::DictArgs d{};
-  d.off = d_off;
-  d.key = d_key;
-  d.thr = d_thr;
-  d.n_ent = d_n_ent;
-  if (int rc = exact_io(c, x, a)) return rc;
-  if (x && (!x->xa_st || !x->xa_n || !x->xa_ptr)) return fail(c, SST_E_ARG, "final dict: the exact-mode answers");
-  big_args(c, a);
+  d.off = x->off;
+  d.key = x->key;
+  d.thr = x->thr;
+  d.n_ent = x->n_ent;
+  if (int rc = exact_io(c, xio, a)) return rc;
+  if (xio && (!xio->xa_st || !xio->xa_n || !xio->xa_ptr))
+    return fail(c, SST_E_ARG, "final dict: the exact-mode answers");
   Prof p(c, SST_K_DICT);
   HIP_OK(c, sst::launch_dict(t->args, a, d, 0, c->n_cu, c->stream));
   return SST_OK;
 }
 
-extern "C" int sst_dict_list_device(sst_table* t, const int64_t* d_peak_off, int64_t n_spec, const double* d_rows_su,
-                                    const double* d_rows_ob, const uint32_t* d_rows_meta, const uint8_t* d_alive,
-                                    const uint32_t* d_rows, double max_weight, double tol, uint32_t* d_err,
-                                    const sst_exact_io* x) {
-  if (!t || !x || n_spec < 0 || n_spec > INT32_MAX ||
-      (n_spec > 0 && (!d_peak_off || !d_rows_su || !d_rows_ob || !d_rows_meta || !d_alive || !d_rows || !d_err)))
-    return SST_E_ARG;
+extern "C" int sst_dict_list_device(sst_table* t, const sst_row_slots* rows, const sst_dict_args* x, uint32_t* d_err,
+                                    const sst_exact_io* xio) {
+  sst::PipeArgs a;
+  if (!xio) return SST_E_ARG;
+  if (int rc = dict_rows(t, rows, x, d_err, a)) return rc;
   sst_ctx* c = t->ctx;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  if (int rc = set_device(c)) return rc;
-  sst::PipeArgs a{};
-  a.peak_off = d_peak_off;
-  a.n_spec = n_spec;
-  a.r_su = const_cast<double*>(d_rows_su);
-  a.r_ob = const_cast<double*>(d_rows_ob);
-  a.r_meta = const_cast<uint32_t*>(d_rows_meta);
-  a.alive = const_cast<uint8_t*>(d_alive);
-  a.cnt = const_cast<uint32_t*>(d_rows);
-  a.max_weight = max_weight;
-  a.tol = tol;
-  a.err = d_err;
-  if (int rc = exact_io(c, x, a)) return rc;
+  StageScope s(t, false, &a);
+  if (s.rc) return s.rc;
+  if (int rc = exact_io(c, xio, a)) return rc;
   sst::DictArgs d{};
-  big_args(c, a);
   Prof p(c, SST_K_DICT);
   HIP_OK(c, sst::launch_dict(t->args, a, d, 2, c->n_cu, c->stream));
   return SST_OK;
 }
 
-extern "C" int sst_fix_finish_device(sst_table* t, int64_t n_spec, const uint32_t* d_rows, const uint64_t* d_alpha,
-                                     uint64_t* d_alpha_next,
-                                     const uint8_t* d_active, uint8_t* d_active_next, uint32_t* d_rounds,
-                                     uint32_t* d_queries, uint32_t* d_n_active, uint32_t* d_err,
+extern "C" int sst_fix_finish_device(sst_table* t, const sst_row_slots* rows, const sst_fix_args* f, uint32_t* d_err,
                                      const sst_exact_io* x) {
-  if (!t || !x || n_spec < 0 || n_spec > INT32_MAX ||
-      (n_spec > 0 && (!d_rows || !d_alpha || !d_alpha_next || !d_active || !d_active_next || !d_rounds || !d_queries ||
-                      !d_n_active || !d_err || !x->xa_st || !x->xa_n || !x->xa_ptr)))
-    return SST_E_ARG;
+  sst::PipeArgs a;
+  if (!x) return SST_E_ARG;
+  if (int rc = row_slots(t, rows, f, kRowCnt, a)) return rc;
+  if ((!fix_args(f, d_err, a) || !x->xa_st || !x->xa_n || !x->xa_ptr) && a.n_spec > 0) return SST_E_ARG;
   sst_ctx* c = t->ctx;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  if (int rc = set_device(c)) return rc;
-  sst::PipeArgs a{};
-  a.n_spec = n_spec;
-  a.cnt = const_cast<uint32_t*>(d_rows);
-  a.alpha = d_alpha;
-  a.alpha_next = d_alpha_next;
-  a.active = d_active;
-  a.active_next = d_active_next;
-  a.rounds = d_rounds;
-  a.queries = d_queries;
-  a.n_active = d_n_active;
-  a.err = d_err;
-  for (int r = 1; r < t->n_rows; ++r)
-    if (!t->is_mod[r]) a.canon[r >> 6] |= 1ull << (r & 63);
+  StageScope s(t, false, &a);
+  if (s.rc) return s.rc;
+  canon_rows(t, a);
   if (int rc = exact_io(c, x, a)) return rc;
-  big_args(c, a);
   Prof p(c, SST_K_FIX_ROUND);
   HIP_OK(c, sst::launch_fix_finish(a, c->n_cu, c->stream));
   return SST_OK;
@@ -3241,21 +2948,43 @@ extern "C" int sst_reach_rows_device(sst_table* t, const uint64_t* d_alpha, cons
 constexpr uint32_t kReachUnits = 4096;
 constexpr size_t kReachMemoBytes = 96ull << 30;  // the replay's memo workspace per launch (HBM: 288 GB)
 
-extern "C" int sst_length_bounds_reach_device(sst_table* t, const double* d_su, const double* d_obs,
-                                              const int32_t* d_spec, const uint64_t* d_alpha,
+// both engines' check of their queries (false: SST_E_ARG)
+static bool length_queries_ok(const sst_table* t, const sst_length_queries* q) {
+  return t && q && q->n >= 0 && q->n <= INT32_MAX && q->max_len >= 0 && !(q->qlen && (!q->caps_len || !q->a0_len)) &&
+         !(q->n > 0 && (!q->su || !q->obs || !q->spec || !q->alpha || !q->lower || !q->upper || !q->status));
+}
+
+// both engines' list pass over the queries (windows, extents; every live query listed)
+static LBArgs length_list_args(const sst_table* t, const sst_length_queries& lq, DevBuf& d_list, DevBuf& d_cnt) {
+  LBArgs q{};
+  q.su = lq.su;
+  q.obs = lq.obs;
+  q.n = lq.n;
+  q.tol = lq.tol;
+  q.prec = lq.prec;
+  q.rprec = 1.0 / lq.prec;
+  q.A0 = (int)std::max<int64_t>(0, std::min<int64_t>(lq.max_mods, kInfBudget));
+  q.max_len = lq.max_len;
+  q.out = lq.lower;
+  q.status = lq.status;
+  q.exact_list = (uint32_t*)d_list.p;
+  q.exact_count = (uint32_t*)d_cnt.p;
+  q.node_budget = kLBNodeBudget;
+  q.alpha = lq.alpha;
+  q.spec = lq.spec;
+  q.comp = (int)t->C;
+  return q;
+}
+
+extern "C" int sst_length_bounds_reach_device(sst_table* t, const sst_length_queries* lq,
                                               const uint32_t* d_reach_bits, const uint64_t* d_reach_off,
-                                              const int64_t* d_reach_words, int64_t n, double tol, double prec,
-                                              int max_len, int64_t max_mods, int64_t* d_lower, int64_t* d_upper,
-                                              int8_t* d_status, const int32_t* d_qlen, const int32_t* d_caps_len,
-                                              const int32_t* d_a0_len, uint64_t* d_nodes, int64_t soft_nodes,
-                                              uint32_t memo_first, int fuse) {
-  if (!t || n < 0 || n > INT32_MAX || max_len < 0 || (d_qlen && (!d_caps_len || !d_a0_len)) ||
-      (n > 0 && (!d_su || !d_obs || !d_spec || !d_alpha || !d_reach_bits || !d_reach_off || !d_reach_words ||
-                 !d_lower || !d_upper || !d_status)))
-    return SST_E_ARG;
+                                              const int64_t* d_reach_words, int64_t soft_nodes, uint32_t memo_first,
+                                              int fuse) {
+  if (!length_queries_ok(t, lq) || (lq->n > 0 && (!d_reach_bits || !d_reach_off || !d_reach_words))) return SST_E_ARG;
+  const int64_t n = lq->n;
   sst_ctx* c = t->ctx;
   std::lock_guard<std::recursive_mutex> g(c->mu);
-  if (max_len > 120) return fail(c, SST_E_ARG, "length bounds (replay): max_len above 120 (the int8 value slots)");
+  if (lq->max_len > 120) return fail(c, SST_E_ARG, "length bounds (replay): max_len above 120 (the int8 value slots)");
   if (int rc = set_device(c)) return rc;
   if (n == 0) return SST_OK;
   // the memo workspace: at most kReachMemoBytes, and at most 60 % of what the
@@ -3270,33 +2999,16 @@ extern "C" int sst_length_bounds_reach_device(sst_table* t, const double* d_su, 
   DevBuf d_list, d_cnt;
   if (!d_list.ensure(nn * 4) || !d_cnt.ensure(4)) return fail(c, SST_E_NOMEM, "device allocation failed (length bound)");
   HIP_OK(c, hipMemsetAsync(d_cnt.p, 0, 4, c->stream));
-  LBArgs q{};
-  q.su = d_su;
-  q.obs = d_obs;
-  q.n = n;
-  q.tol = tol;
-  q.prec = prec;
-  q.rprec = 1.0 / prec;
-  q.A0 = (int)std::max<int64_t>(0, std::min<int64_t>(max_mods, kInfBudget));
-  q.dir = 0;
-  q.max_len = max_len;
-  q.out = d_lower;
-  q.status = d_status;
-  q.exact_list = (uint32_t*)d_list.p;
-  q.exact_count = (uint32_t*)d_cnt.p;
-  q.node_budget = kLBNodeBudget;
-  q.alpha = d_alpha;
-  q.spec = d_spec;
-  q.comp = (int)t->C;
+  LBArgs q = length_list_args(t, *lq, d_list, d_cnt);
   q.reach_bits = d_reach_bits;
   q.reach_off = d_reach_off;
   q.reach_words = d_reach_words;
   q.both = 1;
-  q.out_hi = d_upper;
-  q.qlen = d_qlen;
-  q.caps_len = d_caps_len;
-  q.a0_len = d_a0_len;
-  q.nodes_out = d_nodes;
+  q.out_hi = lq->upper;
+  q.qlen = lq->qlen;
+  q.caps_len = lq->caps_len;
+  q.a0_len = lq->a0_len;
+  q.nodes_out = lq->nodes;
   q.fuse = fuse ? 1 : 0;  // the caller checks every alphabet has <= 64 kept rows
   if (soft_nodes > 0) {
     q.node_budget = (uint64_t)soft_nodes;
@@ -3335,7 +3047,7 @@ extern "C" int sst_length_bounds_reach_device(sst_table* t, const double* d_su, 
       HIP_OK(c, launch_length_bound(t->args, q, (char*)hash.p, (int8_t*)vals.p, (char*)frames.p, cap, units, false,
                                     c->stream));
     }
-    HIP_OK(c, hipMemcpyAsync(st.data(), d_status, nn, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(c, hipMemcpyAsync(st.data(), lq->status, nn, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(c, hipStreamSynchronize(c->stream));
     // the queries whose memo ran out: again, alone, with 8x the memo
     std::vector<uint32_t> retry;
@@ -3384,14 +3096,10 @@ uint64_t pow2_floor(uint64_t x) {
 }
 }  // namespace
 
-static int lbf_frontier(sst_table* t, sst_ctx::LbfWs& W, const double* d_su, const double* d_obs,
-                        const int32_t* d_spec, const uint64_t* d_alpha, const uint8_t* d_lr, const uint64_t* d_lr_off,
-                        int64_t n, double tol, double prec, int max_len, int64_t max_mods, int64_t* d_lower,
-                        int64_t* d_upper, int8_t* d_status, const int32_t* d_qlen, const int32_t* d_caps_len,
-                        const int32_t* d_a0_len, uint64_t* d_nodes, uint64_t workspace_bytes, sst_lbf_stats* stats) {
-  if (!t || n < 0 || n > INT32_MAX || max_len < 0 || (d_qlen && (!d_caps_len || !d_a0_len)) ||
-      (n > 0 && (!d_su || !d_obs || !d_spec || !d_alpha || !d_lr || !d_lr_off || !d_lower || !d_upper || !d_status)))
-    return SST_E_ARG;
+static int lbf_frontier(sst_table* t, sst_ctx::LbfWs& W, const sst_length_queries& lq, const uint8_t* d_lr,
+                        const uint64_t* d_lr_off, uint64_t workspace_bytes, sst_lbf_stats* stats) {
+  if (!length_queries_ok(t, &lq) || (lq.n > 0 && (!d_lr || !d_lr_off))) return SST_E_ARG;
+  const int64_t n = lq.n;
   sst_ctx* c = t->ctx;
   std::lock_guard<std::recursive_mutex> g(c->mu);
   if (int rc = set_device(c)) return rc;
@@ -3413,23 +3121,7 @@ static int lbf_frontier(sst_table* t, sst_ctx::LbfWs& W, const double* d_su, con
   HIP_OK(c, hipMemsetAsync(d_cnt.p, 0, 4, c->stream));
   // the list pass: windows, the reduced table's extent (SST_OUT_OF_TABLE /
   // SST_ABORTED in its last word), empty windows; every live query listed
-  LBArgs q{};
-  q.su = d_su;
-  q.obs = d_obs;
-  q.n = n;
-  q.tol = tol;
-  q.prec = prec;
-  q.rprec = 1.0 / prec;
-  q.A0 = (int)std::max<int64_t>(0, std::min<int64_t>(max_mods, kInfBudget));
-  q.max_len = max_len;
-  q.out = d_lower;
-  q.status = d_status;
-  q.exact_list = (uint32_t*)d_list.p;
-  q.exact_count = (uint32_t*)d_cnt.p;
-  q.node_budget = kLBNodeBudget;
-  q.alpha = d_alpha;
-  q.spec = d_spec;
-  q.comp = (int)t->C;
+  const LBArgs q = length_list_args(t, lq, d_list, d_cnt);
   uint32_t n_live = 0;
   {
     Prof p(c, SST_K_LENGTH_BOUND);
@@ -3496,27 +3188,27 @@ static int lbf_frontier(sst_table* t, sst_ctx::LbfWs& W, const double* d_su, con
     a.list = (const uint32_t*)d_list.p;
     a.chunk0 = c0;
     a.n_chunk = nc;
-    a.su = d_su;
-    a.obs = d_obs;
-    a.tol = tol;
-    a.prec = prec;
-    a.rprec = 1.0 / prec;
-    a.spec = d_spec;
-    a.alpha = d_alpha;
+    a.su = lq.su;
+    a.obs = lq.obs;
+    a.tol = lq.tol;
+    a.prec = lq.prec;
+    a.rprec = 1.0 / lq.prec;
+    a.spec = lq.spec;
+    a.alpha = lq.alpha;
     a.lr = d_lr;
     a.lr_off = d_lr_off;
-    a.qlen = d_qlen;
-    a.caps_len = d_caps_len;
-    a.a0_len = d_a0_len;
+    a.qlen = lq.qlen;
+    a.caps_len = lq.caps_len;
+    a.a0_len = lq.a0_len;
     a.A0 = q.A0;
-    a.max_len = max_len;
+    a.max_len = lq.max_len;
     a.wb = wb;
     a.ring = ring;
     a.jump = jump;
-    a.lower = d_lower;
-    a.upper = d_upper;
-    a.status = d_status;
-    a.nodes_out = d_nodes;
+    a.lower = lq.lower;
+    a.upper = lq.upper;
+    a.status = lq.status;
+    a.nodes_out = lq.nodes;
     if (!qi.ensure((size_t)nc * sizeof(FQInfo)) || !qrow.ensure((size_t)nc * 128 * 4) || !ncnt.ensure((size_t)nc * 4))
       return fail(c, SST_E_NOMEM, "device allocation failed (length-bound frontier queries)");
     a.qi = (FQInfo*)qi.p;
@@ -3604,7 +3296,7 @@ static int lbf_frontier(sst_table* t, sst_ctx::LbfWs& W, const double* d_su, con
         HIP_OK(c, hipMemcpyAsync(&one, qi.p, sizeof(FQInfo), hipMemcpyDeviceToHost, c->stream));
         HIP_OK(c, hipStreamSynchronize(c->stream));
         const int8_t ab = SST_ABORTED;
-        HIP_OK(c, hipMemcpyAsync(d_status + one.i, &ab, 1, hipMemcpyHostToDevice, c->stream));
+        HIP_OK(c, hipMemcpyAsync(lq.status + one.i, &ab, 1, hipMemcpyHostToDevice, c->stream));
         if (stats) stats->aborted++;
         return 1;
       }
@@ -3674,17 +3366,253 @@ static int lbf_frontier(sst_table* t, sst_ctx::LbfWs& W, const double* d_su, con
   return SST_OK;
 }
 
-extern "C" int sst_length_bounds_frontier_device(sst_table* t, const double* d_su, const double* d_obs,
-                                                 const int32_t* d_spec, const uint64_t* d_alpha, const uint8_t* d_lr,
-                                                 const uint64_t* d_lr_off, int64_t n, double tol, double prec,
-                                                 int max_len, int64_t max_mods, int64_t* d_lower, int64_t* d_upper,
-                                                 int8_t* d_status, const int32_t* d_qlen, const int32_t* d_caps_len,
-                                                 const int32_t* d_a0_len, uint64_t* d_nodes, uint64_t workspace_bytes,
+extern "C" int sst_length_bounds_frontier_device(sst_table* t, const sst_length_queries* q, const uint8_t* d_lr,
+                                                 const uint64_t* d_lr_off, uint64_t workspace_bytes,
                                                  sst_lbf_stats* stats) {
-  if (!t) return SST_E_ARG;
-  return lbf_frontier(t, t->ctx->lbf, d_su, d_obs, d_spec, d_alpha, d_lr, d_lr_off, n, tol, prec, max_len, max_mods,
-                      d_lower, d_upper, d_status, d_qlen, d_caps_len, d_a0_len, d_nodes, workspace_bytes, stats);
+  if (!t || !q) return SST_E_ARG;
+  return lbf_frontier(t, t->ctx->lbf, *q, d_lr, d_lr_off, workspace_bytes, stats);
 }
+
+namespace {
+constexpr uint64_t kBatchFrontierBytes = 4ull << 30;  // sst_length_bound_batch's frontier workspace
+
+static int length_bound_batch(sst_table* t, const double* su, const double* obs, int64_t n, double tol, double prec,
+                              int max_len, int64_t max_mods, int direction, int64_t* out, int8_t* status,
+                              const int32_t* spec, const uint64_t* alpha, int64_t n_alpha) {
+  const bool exact_only = (direction & SST_LB_EXACT_ONLY) != 0;
+  const bool replay_only = (direction & SST_LB_REPLAY) != 0;
+  direction &= ~(SST_LB_EXACT_ONLY | SST_LB_REPLAY);
+  if (!t || n < 0 || n > INT32_MAX || (n > 0 && (!su || !obs || !out || !status)) || (direction != 0 && direction != 1) ||
+      max_len < 0 || max_len > 253)
+    return SST_E_ARG;
+  sst_ctx* c = t->ctx;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  if (int rc = set_device(c)) return rc;
+  if (n == 0) return SST_OK;
+  const size_t nn = (size_t)n;
+  DevBuf d_su, d_obs, d_out, d_st, d_list, d_cnt, layers, d_spec, d_alpha;
+  if (!d_su.ensure(nn * 8) || !d_obs.ensure(nn * 8) || !d_out.ensure(nn * 8) || !d_st.ensure(nn) ||
+      !d_list.ensure(nn * 4) || !d_cnt.ensure(4))
+    return fail(c, SST_E_NOMEM, "device allocation failed (length bound)");
+  if (alpha) {
+    for (int64_t i = 0; spec && i < n; ++i)
+      if (spec[i] < 0 || spec[i] >= n_alpha) return fail(c, SST_E_ARG, "length bound: alphabet index out of range");
+    if (!d_alpha.ensure((size_t)n_alpha * 16) || (spec && !d_spec.ensure(nn * 4)))
+      return fail(c, SST_E_NOMEM, "device allocation failed (length bound alphabets)");
+    HIP_OK(c, hipMemcpyAsync(d_alpha.p, alpha, (size_t)n_alpha * 16, hipMemcpyHostToDevice, c->stream));
+    if (spec) HIP_OK(c, hipMemcpyAsync(d_spec.p, spec, nn * 4, hipMemcpyHostToDevice, c->stream));
+  }
+  HIP_OK(c, hipMemcpyAsync(d_su.p, su, nn * 8, hipMemcpyHostToDevice, c->stream));
+  HIP_OK(c, hipMemcpyAsync(d_obs.p, obs, nn * 8, hipMemcpyHostToDevice, c->stream));
+  HIP_OK(c, hipMemsetAsync(d_cnt.p, 0, 4, c->stream));
+  LBArgs q{};
+  q.su = (const double*)d_su.p;
+  q.obs = (const double*)d_obs.p;
+  q.n = n;
+  q.tol = tol;
+  q.prec = prec;
+  q.rprec = 1.0 / prec;
+  q.A0 = (int)std::max<int64_t>(0, std::min<int64_t>(max_mods, kInfBudget));  // round(rate * max_len) >= 0
+  q.dir = direction;
+  q.max_len = max_len;
+  q.out = (int64_t*)d_out.p;
+  q.status = (int8_t*)d_st.p;
+  q.exact_list = (uint32_t*)d_list.p;
+  q.exact_count = (uint32_t*)d_cnt.p;
+  q.node_budget = kLBNodeBudget;
+  q.alpha = alpha ? (const uint64_t*)d_alpha.p : nullptr;
+  q.spec = alpha && spec ? (const int32_t*)d_spec.p : nullptr;
+  q.comp = (int)t->C;
+  // fast path: layered reachability up to the largest window (a host-side
+  // over-estimate; the kernel re-checks hi < layer_limit exactly), kept below
+  // the reference's masked last column
+  if (t->closure && t->args.w_min > 0 && !exact_only && !alpha) {
+    double hmax = 0;
+    for (int64_t i = 0; i < n; ++i) hmax = std::max(hmax, (su[i] + tol * std::fabs(obs[i])) / prec + 4.0);
+    const int64_t safe = (t->n_cols - 1) * t->C;
+    const int64_t lim = std::min<int64_t>(safe, (int64_t)std::min(hmax, (double)safe));
+    if (lim > 0) {
+      const int64_t words = (lim + 63) / 64;
+      const int n_layers = (int)(lim / t->args.w_min) + 2;
+      if (!layers.ensure((size_t)n_layers * words * 8)) return fail(c, SST_E_NOMEM, "device allocation failed (layers)");
+      uint64_t* L = (uint64_t*)layers.p;
+      const uint64_t one = 1;
+      HIP_OK(c, hipMemsetAsync(L, 0, (size_t)words * 8, c->stream));
+      HIP_OK(c, hipMemcpyAsync(L, &one, 8, hipMemcpyHostToDevice, c->stream));
+      for (int k = 0; k + 1 < n_layers; ++k)
+        HIP_OK(c, launch_layer_step(L + (size_t)k * words, L + (size_t)(k + 1) * words, words, t->args.w, t->n_rows,
+                                    c->stream));
+      q.layers = L;
+      q.layer_words = words;
+      q.n_layers = n_layers;
+      q.layer_limit = lim;
+    }
+  }
+  // fast kernel (queues the rest), then the exact kernel; retried with a
+  // larger per-lane memo while any query reports hash exhaustion
+  uint32_t n_exact = 0;
+  {
+    Prof p(c, SST_K_LENGTH_BOUND);
+    HIP_OK(c, launch_length_bound(t->args, q, nullptr, nullptr, nullptr, 0, 0, true, c->stream));
+  }
+  HIP_OK(c, hipMemcpyAsync(&n_exact, d_cnt.p, 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(c, hipStreamSynchronize(c->stream));
+  std::vector<int8_t> st(nn);
+  DevBuf f_alpha, f_words, f_off, f_bits, f_lr, f_lro, f_spec, f_lo, f_hi, f_st;
+  bool frontier_ok = t->closure && !alpha && !replay_only && t->args.w_min >= 1024;  // (the reach rows' LDS ring)
+  int64_t w_top = 0;
+  for (int r = 1; r < t->n_rows && frontier_ok; ++r) {
+    frontier_ok = t->masses[r] < (1 << 20);
+    w_top = std::max<int64_t>(w_top, t->masses[r]);
+  }
+  // the frontier applies the reduced-alphabet extent ceil((w_top * 35 + 1) / C) * C
+  // (mass_table.py:116): only a table of exactly that extent (every table built
+  // here, the reference's cache) is answered by it; an uploaded table of another
+  // extent goes to the replay, which reads the table's own
+  frontier_ok = frontier_ok && (w_top * 35 + t->C) / t->C == t->n_cols;
+  if (n_exact && frontier_ok) {
+    // the first-visit frontier (DESIGN §3) on the table's own rows, both
+    // directions, for the queries the fast path left pending only (its own
+    // answers stay); a window in the table's last packed word, where the
+    // frontier's reachability cannot see the last-column mask (SST_ABORTED
+    // there), or one the frontier's layout cannot hold, goes on to the replay
+    const size_t m = n_exact;
+    std::vector<uint32_t> pend(m);
+    HIP_OK(c, hipMemcpyAsync(pend.data(), d_list.p, m * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    std::vector<double> psu(m), pob(m);
+    int64_t hmax = 1;
+    for (size_t j = 0; j < m; ++j) {
+      psu[j] = su[pend[j]];
+      pob[j] = obs[pend[j]];
+      hmax = std::max<int64_t>(hmax, (int64_t)((psu[j] + tol * std::fabs(pob[j])) / prec) + 4);
+    }
+    hmax = std::min<int64_t>(hmax, t->n_cols * t->C);
+    const int64_t words = hmax / 32 + 2;
+    uint64_t am[2] = {0, 0};
+    for (int r = 1; r < t->n_rows; ++r) am[r >> 6] |= 1ull << (r & 63);
+    const int64_t zero = 0;
+    const size_t K = (size_t)(t->n_rows - 1);
+    DevBuf f_su, f_ob;
+    if (!f_alpha.ensure(16) || !f_words.ensure(8) || !f_off.ensure(8) || !f_bits.ensure(K * words * 4) ||
+        !f_lr.ensure((size_t)words * 32) || !f_lro.ensure(8) || !f_spec.ensure(m * 4) || !f_lo.ensure(m * 8) ||
+        !f_hi.ensure(m * 8) || !f_st.ensure(m) || !f_su.ensure(m * 8) || !f_ob.ensure(m * 8))
+      return fail(c, SST_E_NOMEM, "device allocation failed (length bound, frontier)");
+    HIP_OK(c, hipMemcpyAsync(f_alpha.p, am, 16, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(c, hipMemcpyAsync(f_words.p, &words, 8, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(c, hipMemcpyAsync(f_off.p, &zero, 8, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(c, hipMemcpyAsync(f_lro.p, &zero, 8, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(c, hipMemcpyAsync(f_su.p, psu.data(), m * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(c, hipMemcpyAsync(f_ob.p, pob.data(), m * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(c, hipMemsetAsync(f_spec.p, 0, m * 4, c->stream));
+    if (int rc = sst_reach_rows_device(t, (const uint64_t*)f_alpha.p, (const int64_t*)f_words.p,
+                                       (const uint64_t*)f_off.p, 1, (uint32_t*)f_bits.p))
+      return rc;
+    if (int rc = sst_reach_lowest_device(t, (const uint64_t*)f_alpha.p, (const int64_t*)f_words.p,
+                                         (const uint64_t*)f_off.p, 1, (const uint32_t*)f_bits.p,
+                                         (const uint64_t*)f_lro.p, (uint8_t*)f_lr.p))
+      return rc;
+    sst_length_queries fq{};
+    fq.su = (const double*)f_su.p;
+    fq.obs = (const double*)f_ob.p;
+    fq.spec = (const int32_t*)f_spec.p;
+    fq.alpha = (const uint64_t*)f_alpha.p;
+    fq.n = (int64_t)m;
+    fq.tol = tol;
+    fq.prec = prec;
+    fq.max_len = max_len;
+    fq.max_mods = max_mods;
+    fq.lower = (int64_t*)f_lo.p;
+    fq.upper = (int64_t*)f_hi.p;
+    fq.status = (int8_t*)f_st.p;
+    if (int rc = lbf_frontier(t, c->lbf_small, fq, (const uint8_t*)f_lr.p, (const uint64_t*)f_lro.p,
+                              kBatchFrontierBytes, nullptr))
+      return rc;
+    // scatter the frontier's answers over the fast pass's (host copies: nn x 9 bytes)
+    std::vector<int64_t> fv(m), ov(nn);
+    std::vector<int8_t> fs(m);
+    HIP_OK(c, hipMemcpyAsync(fv.data(), direction ? f_hi.p : f_lo.p, m * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(c, hipMemcpyAsync(fs.data(), f_st.p, m, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(c, hipMemcpyAsync(ov.data(), d_out.p, nn * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(c, hipMemcpyAsync(st.data(), d_st.p, nn, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    std::vector<uint32_t> rest;
+    for (size_t j = 0; j < m; ++j) {
+      ov[pend[j]] = fv[j];
+      st[pend[j]] = fs[j];
+      if (fs[j] == SST_ABORTED) rest.push_back(pend[j]);
+    }
+    HIP_OK(c, hipMemcpyAsync(d_out.p, ov.data(), nn * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(c, hipMemcpyAsync(d_st.p, st.data(), nn, hipMemcpyHostToDevice, c->stream));
+    n_exact = (uint32_t)rest.size();
+    if (n_exact) {
+      HIP_OK(c, hipMemcpyAsync(d_list.p, rest.data(), rest.size() * 4, hipMemcpyHostToDevice, c->stream));
+      HIP_OK(c, hipMemcpyAsync(d_cnt.p, &n_exact, 4, hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_OK(c, hipStreamSynchronize(c->stream));  // the host vectors above are read by the copies
+  }
+  if (n_exact && max_len > 120)  // the frontier answers up to 253; the replay's int8 value slots hold 121
+    return fail(c, SST_E_ARG,
+                "length bound: max_len " + std::to_string(max_len) + " above 120 for a window only the DFS replay "
+                "answers (the table's last packed word, or beyond the frontier's layout)");
+  if (n_exact) {
+    // one 64-lane block per query in flight (k_length_exact<WAVE>), each with
+    // its own memo slice: up to 1 024 at once (4 waves per CU; the memo slices
+    // then take ~10 GB of HBM), batches of many spectra keep the chip busy
+    int units = (int)std::min<uint32_t>(1024, n_exact);
+    uint32_t cap = memo_cap0(units, kLBHashCap0);
+    for (;;) {
+      DevBuf hash, vals, frames;
+      if (!hash.ensure((size_t)units * cap * hash_entry_bytes()) || !vals.ensure((size_t)units * cap * kMaxRows) ||
+          !frames.ensure((size_t)units * lb_frame_bytes()))
+        return fail(c, SST_E_NOMEM, "device allocation failed (length-bound memo)");
+      HIP_OK(c, hipMemsetAsync(hash.p, 0, hash.bytes, c->stream));
+      Prof p(c, SST_K_LENGTH_BOUND);
+      HIP_OK(c, launch_length_bound(t->args, q, (char*)hash.p, (int8_t*)vals.p, (char*)frames.p, cap, units, false,
+                                    c->stream));
+      HIP_OK(c, hipMemcpyAsync(st.data(), d_st.p, nn, hipMemcpyDeviceToHost, c->stream));
+      HIP_OK(c, hipStreamSynchronize(c->stream));
+      bool retry = false;
+      for (size_t i = 0; i < nn; ++i) retry |= st[i] == kStatusExactRetry;
+      if (!retry) break;
+      if ((size_t)std::max(1, units / 8) * cap * 8 * (hash_entry_bytes() + kMaxRows) > kMaxMemoBytes)
+        return fail(c, SST_E_NOMEM, "length bound: memo would exceed the workspace limit");
+      cap *= 8;
+      units = std::max(1, units / 8);
+    }
+  }
+  HIP_OK(c, hipMemcpyAsync(out, d_out.p, nn * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(c, hipMemcpyAsync(status, d_st.p, nn, hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(c, hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < nn; ++i)
+    if (status[i] == kStatusPending || status[i] == kStatusExactRetry)
+      return fail(c, SST_E_INTERNAL, "length bound: query left unresolved (internal error)");
+  return SST_OK;
+}
+
+}  // namespace
+extern "C" {
+
+int sst_length_bound_batch(sst_table* t, const double* su, const double* obs, int64_t n, double tol, double prec,
+                           int max_len, int64_t max_mods, int direction, int64_t* out, int8_t* status) {
+  return length_bound_batch(t, su, obs, n, tol, prec, max_len, max_mods, direction, out, status, nullptr, nullptr,
+                            0);
+}
+
+int sst_length_bound_alpha_batch(sst_table* t, const double* su, const double* obs, const int32_t* spec,
+                                 const uint64_t* alpha, int64_t n_alpha, int64_t n, double tol, double prec,
+                                 int max_len, int64_t max_mods, int direction, int64_t* out, int8_t* status) {
+  // "lower" only: a left child that is reachable in the full table but not with
+  // the kept rows returns the default (-1) there, and the reference's upper
+  // bound counts such a visited child as -1 + 1 = 0 where the rebuilt table
+  // would not visit it at all (DESIGN §3); the lower bound's default (max_len
+  // + 1) can never win a min, so its masked replay is exact
+  if (!alpha || n_alpha <= 0 || (direction & ~SST_LB_EXACT_ONLY) != 0) return SST_E_ARG;
+  return length_bound_batch(t, su, obs, n, tol, prec, max_len, max_mods, direction, out, status, spec, alpha,
+                            n_alpha);
+}
+
+}  // extern "C"
 
 extern "C" int sst_jaccard_device(sst_table* t, const sst_jaccard_args* a) {
   if (!t || !a || a->n_spec < 0) return SST_E_ARG;

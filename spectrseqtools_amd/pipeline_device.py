@@ -21,6 +21,7 @@ arrays; a spectrum outside a per-spectrum engine limit (DeviceLimits) runs
 the host mirror instead and is spliced in at its position.
 """
 import ctypes
+import dataclasses
 import os
 import sys
 import time
@@ -170,6 +171,11 @@ class DeviceRows:
     valid: object      # torch int8 [4 P] A7 codes (breakage-major) or None
     names: list        # breakage label per code
 
+    def slots(self):
+        """The rows as the stages take them (sst_row_slots), from the live tensors."""
+        return _native.RowSlots(len(self.peak_off) - 1, self.peak_off.data_ptr(), self.su.data_ptr(),
+                                self.obs.data_ptr(), self.meta.data_ptr(), self.alive.data_ptr(), self.rows.data_ptr())
+
 
 @_one_stream
 def classify_device(dp_table, obs, offsets, su_seq, breakage_dict, intensity=None, intensity_cutoff=0.5e6,
@@ -208,15 +214,16 @@ def classify_device(dp_table, obs, offsets, su_seq, breakage_dict, intensity=Non
     valid = torch.empty(max(1, len(weights) * P), dtype=torch.int8, device=dev) if keep_valid else None
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     torch.cuda.synchronize(dev)
-    eng.check(eng._lib.sst_classify_rows_device(
-        dp_table.device_table.handle, obs_t.data_ptr(), off_t.data_ptr(), S, P,
-        None if int_t is None else int_t.data_ptr(), float(intensity_cutoff), float(mass_cutoff), su_t.data_ptr(),
-        _native._ptr(shifts), _native._ptr(sides), len(shifts), float(max_w), float(dp_table.tolerance),
-        float(dp_table.precision), None if valid is None else valid.data_ptr(), su.data_ptr(), ob.data_ptr(),
-        meta.data_ptr(), alive.data_ptr(), rows.data_ptr(), err.data_ptr()), "sst_classify_rows_device")
+    out = DeviceRows(off_t, su, ob, meta, alive, rows, valid, names)
+    a = _native.ClassifyArgs(obs_t.data_ptr(), P, None if int_t is None else int_t.data_ptr(), float(intensity_cutoff),
+                             float(mass_cutoff), su_t.data_ptr(), shifts.ctypes.data, sides.ctypes.data, len(shifts),
+                             float(max_w), float(dp_table.tolerance), float(dp_table.precision),
+                             None if valid is None else valid.data_ptr())
+    eng.check(eng._lib.sst_classify_rows_device(dp_table.device_table.handle, ctypes.byref(out.slots()),
+                                                ctypes.byref(a), err.data_ptr()), "sst_classify_rows_device")
     eng.synchronize()
     _check_err(err)
-    return DeviceRows(off_t, su, ob, meta, alive, rows, valid, names)
+    return out
 
 
 def _max_weight(explanation_masses=None):
@@ -282,11 +289,10 @@ class _ExactLists:
         n_q = torch.zeros(max(1, S), dtype=torch.int32, device=self.dev)
         off = torch.zeros(S + 1, dtype=torch.int64, device=self.dev)
         err = torch.zeros(1, dtype=torch.int32, device=self.dev)
-        eng.check(eng._lib.sst_dict_count_device(dp.device_table.handle, r.peak_off.data_ptr(), S, r.su.data_ptr(),
-                                                 r.obs.data_ptr(), r.meta.data_ptr(), r.alive.data_ptr(),
-                                                 r.rows.data_ptr(), float(_max_weight()), float(dp.tolerance),
-                                                 n_q.data_ptr(), off.data_ptr(), err.data_ptr()),
-                  "sst_dict_count_device")
+        a = _native.DictArgs(max_weight=float(_max_weight()), tol=float(dp.tolerance), n_q=n_q.data_ptr(),
+                             off=off.data_ptr())
+        eng.check(eng._lib.sst_dict_count_device(dp.device_table.handle, ctypes.byref(r.slots()), ctypes.byref(a),
+                                                 err.data_ptr()), "sst_dict_count_device")
         need = int((n_q[:S].to(torch.int64) * (active[:S].to(torch.bool) & self.exact[:S])).sum().item())
         if need > self.cap:
             self._alloc(need)
@@ -352,30 +358,26 @@ def fixpoint_device(dp_table, rows: DeviceRows, max_len, tolerance=None, record=
     h = dp_table.device_table.handle
     history = []
     n_rounds = 0
-    max_w = _max_weight()
+    slots = ctypes.byref(rows.slots())
+    fa = _native.FixArgs(rounds=rounds.data_ptr(), queries=queries.data_ptr(), n_active=n_active.data_ptr(),
+                         max_weight=float(_max_weight()), tol=float(tolerance), prec=float(dp_table.precision))
     torch.cuda.synchronize(dev)
     while True:  # per round: two launches, one synchronize, one 8-byte read
         xp = None
         if xio is not None:  # list capacity: the round's queries of the exact-mode spectra
             xio.prepare(active)
             xp = ctypes.byref(xio.io)
-        eng.check(L.sst_fix_round_device(h, rows.peak_off.data_ptr(), S, rows.su.data_ptr(), rows.obs.data_ptr(),
-                                         rows.meta.data_ptr(), rows.alive.data_ptr(), rows.rows.data_ptr(),
-                                         alpha.data_ptr(), alpha_next.data_ptr(), active.data_ptr(),
-                                         active_next.data_ptr(), rounds.data_ptr(), queries.data_ptr(),
-                                         n_active.data_ptr(), float(max_w), float(tolerance),
-                                         float(dp_table.precision), err.data_ptr(), xp), "sst_fix_round_device")
+        fa.alpha, fa.alpha_next = alpha.data_ptr(), alpha_next.data_ptr()
+        fa.active, fa.active_next = active.data_ptr(), active_next.data_ptr()
+        eng.check(L.sst_fix_round_device(h, slots, ctypes.byref(fa), err.data_ptr(), xp), "sst_fix_round_device")
         if xio is not None:  # the listed queries answered exactly, then the exact-mode half of the round
             xio.answer(alpha)
-            eng.check(L.sst_fix_finish_device(h, S, rows.rows.data_ptr(), alpha.data_ptr(), alpha_next.data_ptr(), active.data_ptr(),
-                                              active_next.data_ptr(), rounds.data_ptr(), queries.data_ptr(),
-                                              n_active.data_ptr(), err.data_ptr(), xp), "sst_fix_finish_device")
+            eng.check(L.sst_fix_finish_device(h, slots, ctypes.byref(fa), err.data_ptr(), xp),
+                      "sst_fix_finish_device")
         # re-filter only the spectra whose alphabet shrank: an unchanged alphabet is
         # the table the rows already passed (round 1: classify's full table)
-        eng.check(L.sst_valid_rows_alpha_device(h, rows.peak_off.data_ptr(), S, rows.su.data_ptr(),
-                                                rows.obs.data_ptr(), rows.rows.data_ptr(), alpha_next.data_ptr(),
-                                                active_next.data_ptr(), rows.alive.data_ptr(), float(tolerance),
-                                                float(dp_table.precision), err.data_ptr()),
+        eng.check(L.sst_valid_rows_alpha_device(h, slots, alpha_next.data_ptr(), active_next.data_ptr(),
+                                                float(tolerance), float(dp_table.precision), err.data_ptr()),
                   "sst_valid_rows_alpha_device")
         eng.synchronize()
         n_rounds += 1
@@ -451,12 +453,11 @@ def bins_device(dp_table, rows: DeviceRows, alpha, tolerance=None, max_len=None)
     eng = dp_table.device_table.engine
     L = eng._lib
     h = dp_table.device_table.handle
+    slots = ctypes.byref(rows.slots())
+    ba = _native.BinsArgs(alpha=a.data_ptr(), tol=float(tolerance), prec=float(dp_table.precision),
+                          n_q=n_q.data_ptr(), n_q0=n_q0.data_ptr(), q_off=q_off.data_ptr())
     torch.cuda.synchronize(dev)
-    eng.check(L.sst_bins_count_device(h, rows.peak_off.data_ptr(), S, rows.su.data_ptr(), rows.obs.data_ptr(),
-                                      rows.meta.data_ptr(), rows.alive.data_ptr(), rows.rows.data_ptr(),
-                                      float(tolerance), n_q.data_ptr(), q_off.data_ptr(), err.data_ptr(),
-                                      n_q0.data_ptr()),
-              "sst_bins_count_device")
+    eng.check(L.sst_bins_count_device(h, slots, ctypes.byref(ba), err.data_ptr()), "sst_bins_count_device")
     eng.synchronize()
     _check_err(err)
     total = int(q_off[S].item())
@@ -473,15 +474,10 @@ def bins_device(dp_table, rows: DeviceRows, alpha, tolerance=None, max_len=None)
         d_spec = torch.empty(max(1, total), dtype=torch.int32, device=dev)
         d_q = torch.empty(max(1, total), dtype=torch.int64, device=dev)
         n_def = torch.zeros(1, dtype=torch.int32, device=dev)
-    ptr = (lambda x: x.data_ptr()) if defer else (lambda x: None)
-    eng.check(L.sst_bins_emit_device(h, rows.peak_off.data_ptr(), S, rows.su.data_ptr(), rows.obs.data_ptr(),
-                                     rows.meta.data_ptr(), rows.alive.data_ptr(), rows.rows.data_ptr(), a.data_ptr(),
-                                     float(tolerance), float(dp_table.precision), q_off.data_ptr(),
-                                     status.data_ptr(), count.data_ptr(), ptr(d_mass) if defer else None,
-                                     ptr(d_thr) if defer else None, ptr(d_spec) if defer else None,
-                                     ptr(d_q) if defer else None, ptr(n_def) if defer else None, err.data_ptr(),
-                                     pok.data_ptr() if pok is not None else None),
-              "sst_bins_emit_device")
+        ba.def_mass, ba.def_thr, ba.def_spec = d_mass.data_ptr(), d_thr.data_ptr(), d_spec.data_ptr()
+        ba.def_q, ba.n_def, ba.pair_ok = d_q.data_ptr(), n_def.data_ptr(), None if pok is None else pok.data_ptr()
+    ba.status, ba.count = status.data_ptr(), count.data_ptr()
+    eng.check(L.sst_bins_emit_device(h, slots, ctypes.byref(ba), err.data_ptr()), "sst_bins_emit_device")
     eng.synchronize()
     _check_err(err)
     out = DeviceBins(q_off.cpu().numpy(), status[:total], count[:total], q_off_dev=q_off, q0_dev=n_q0,
@@ -577,17 +573,18 @@ def final_dict_device(dp_table, rows: DeviceRows, alpha_dev, tolerance=None, max
     n_q = torch.zeros(max(1, S), dtype=torch.int32, device=dev)
     off = torch.zeros(S + 1, dtype=torch.int64, device=dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    max_w = _max_weight()
-    args = (h, rows.peak_off.data_ptr(), S, rows.su.data_ptr(), rows.obs.data_ptr(), rows.meta.data_ptr(),
-            rows.alive.data_ptr(), rows.rows.data_ptr())
+    slots = ctypes.byref(rows.slots())
+    da = _native.DictArgs(alpha_dev.data_ptr(), float(_max_weight()), float(tolerance), float(dp_table.precision),
+                          n_q.data_ptr(), off.data_ptr())
+    args = (h, slots, ctypes.byref(da), err.data_ptr())
     torch.cuda.synchronize(dev)
-    eng.check(L.sst_dict_count_device(*args, float(max_w), float(tolerance), n_q.data_ptr(), off.data_ptr(),
-                                      err.data_ptr()), "sst_dict_count_device")
+    eng.check(L.sst_dict_count_device(*args), "sst_dict_count_device")
     eng.synchronize()
     total = int(off[S].item())
     key = torch.empty(max(1, total), dtype=torch.int64, device=dev)
     thr = torch.empty(max(1, total), dtype=torch.float64, device=dev)
     n_ent = torch.zeros(max(1, S), dtype=torch.int32, device=dev)
+    da.key, da.thr, da.n_ent = key.data_ptr(), thr.data_ptr(), n_ent.data_ptr()
     xp = None
     if max_len is not None:
         ok = budgets_pair_ok(dp_table, np.broadcast_to(np.asarray(max_len, dtype=np.int64), (S,)))
@@ -595,12 +592,9 @@ def final_dict_device(dp_table, rows: DeviceRows, alpha_dev, tolerance=None, max
             xio = _ExactLists(dp_table, rows, ok, max_len, cap=total)
             xio.reset()
             xp = ctypes.byref(xio.io)
-            eng.check(L.sst_dict_list_device(*args, float(max_w), float(tolerance), err.data_ptr(), xp),
-                      "sst_dict_list_device")
+            eng.check(L.sst_dict_list_device(*args, xp), "sst_dict_list_device")
             xio.answer(alpha_dev)
-    eng.check(L.sst_dict_build_device(*args, alpha_dev.data_ptr(), float(max_w), float(tolerance),
-                                      float(dp_table.precision), off.data_ptr(), key.data_ptr(), thr.data_ptr(),
-                                      n_ent.data_ptr(), err.data_ptr(), xp), "sst_dict_build_device")
+    eng.check(L.sst_dict_build_device(*args, xp), "sst_dict_build_device")
     eng.synchronize()
     _check_err(err)
     return DeviceDict(off, n_ent, key, thr)
@@ -1021,12 +1015,14 @@ def length_bounds_alpha_device(dp_table, alpha_sk, su, ob, max_len, caps_len, a0
             beat = _Heartbeat("[length] replay running", 30.0) if _PROGRESS else None
             for s0 in range(0, n, length_chunk):
                 s1 = min(n, s0 + length_chunk)
+                q = _native.LengthQueries(
+                    su_t.data_ptr() + 8 * s0, ob_t.data_ptr() + 8 * s0, sp_t.data_ptr() + 4 * s0, al_t.data_ptr(),
+                    s1 - s0, float(tol), float(prec), ml_hi, a0_len[ml_hi], lo_t.data_ptr() + 8 * s0,
+                    up_t.data_ptr() + 8 * s0, st_t.data_ptr() + s0, ql_t.data_ptr() + 4 * s0, caps_t.data_ptr(),
+                    a0_t.data_ptr(), nd_t.data_ptr() + 8 * s0)
                 eng.check(L.sst_length_bounds_reach_device(
-                    h, su_t.data_ptr() + 8 * s0, ob_t.data_ptr() + 8 * s0, sp_t.data_ptr() + 4 * s0, al_t.data_ptr(),
-                    bits.data_ptr(), o_t.data_ptr(), w_t.data_ptr(), s1 - s0, float(tol), float(prec), ml_hi,
-                    a0_len[ml_hi], lo_t.data_ptr() + 8 * s0, up_t.data_ptr() + 8 * s0, st_t.data_ptr() + s0,
-                    ql_t.data_ptr() + 4 * s0, caps_t.data_ptr(), a0_t.data_ptr(), nd_t.data_ptr() + 8 * s0,
-                    int(soft_nodes), int(memo_first), int(K_u.max() <= 64)), "sst_length_bounds_reach_device")
+                    h, ctypes.byref(q), bits.data_ptr(), o_t.data_ptr(), w_t.data_ptr(), int(soft_nodes),
+                    int(memo_first), int(K_u.max() <= 64)), "sst_length_bounds_reach_device")
             if beat is not None:
                 beat.stop()
             idx = members[order]
@@ -1108,11 +1104,13 @@ def length_bounds_alpha_device(dp_table, alpha_sk, su, ob, max_len, caps_len, a0
             nd_t = torch.zeros(n, dtype=torch.int64, device=dev)
             fs = _native.LbfStats()
             beat = _Heartbeat("[length] frontier running", 30.0) if _PROGRESS else None
-            eng.check(L.sst_length_bounds_frontier_device(
-                h, su_t.data_ptr(), ob_t.data_ptr(), sp_t.data_ptr(), alu_t.data_ptr(), lr.data_ptr(),
-                lo_u_t.data_ptr(), n, float(tol), float(prec), ml_hi, a0_len[ml_hi], lo_t.data_ptr(), up_t.data_ptr(),
-                st_t.data_ptr(), ql_t.data_ptr(), caps_t.data_ptr(), a0_t.data_ptr(), nd_t.data_ptr(),
-                int(frontier_workspace), ctypes.byref(fs)), "sst_length_bounds_frontier_device")
+            q = _native.LengthQueries(
+                su_t.data_ptr(), ob_t.data_ptr(), sp_t.data_ptr(), alu_t.data_ptr(), n, float(tol), float(prec), ml_hi,
+                a0_len[ml_hi], lo_t.data_ptr(), up_t.data_ptr(), st_t.data_ptr(), ql_t.data_ptr(), caps_t.data_ptr(),
+                a0_t.data_ptr(), nd_t.data_ptr())
+            eng.check(L.sst_length_bounds_frontier_device(h, ctypes.byref(q), lr.data_ptr(), lo_u_t.data_ptr(),
+                                                          int(frontier_workspace), ctypes.byref(fs)),
+                      "sst_length_bounds_frontier_device")
             if beat is not None:
                 beat.stop()
             lower[members] = lo_t.cpu().numpy()
@@ -1296,10 +1294,9 @@ def post_skeleton_device(dp_table, rows: DeviceRows, sk: DeviceSkeleton, ln: Dev
     alive_skel = alive_out.clone()
     before = int(alive_out.sum().item())
     err2 = torch.zeros(1, dtype=torch.int32, device=dev)
-    eng.check(L.sst_valid_rows_alpha_device(h, rows.peak_off.data_ptr(), S, rows.su.data_ptr(), rows.obs.data_ptr(),
-                                            rows.rows.data_ptr(), alpha_out.data_ptr(), active.data_ptr(),
-                                            alive_out.data_ptr(), float(tol), float(dp_table.precision),
-                                            err2.data_ptr()), "sst_valid_rows_alpha_device")
+    eng.check(L.sst_valid_rows_alpha_device(h, ctypes.byref(dataclasses.replace(rows, alive=alive_out).slots()),
+                                            alpha_out.data_ptr(), active.data_ptr(), float(tol),
+                                            float(dp_table.precision), err2.data_ptr()), "sst_valid_rows_alpha_device")
     eng.synchronize()
     if int(err.item()):
         raise _native.EngineError(f"post-skeleton stage: a spectrum of more than {MAX_PEAKS} peaks")

@@ -48,6 +48,55 @@ def test_library_targets_gfx950(tmp_path):
     assert "gfx950" in text
 
 
+def header_struct_fields(name):
+    """[(field, base type, is pointer, array length or None)] of a header struct, in its order."""
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    body = re.search(rf"typedef struct {name} \{{(.*?)\}} {name};", src, flags=re.S).group(1)
+    out = []
+    for stmt in filter(None, (s.strip() for s in body.split(";"))):
+        base, rest = re.fullmatch(r"(?:const\s+)?(\w+)\b\s*(.*)", stmt, flags=re.S).groups()
+        for decl in rest.split(","):
+            star, field, length = re.fullmatch(r"\s*(\*?)\s*(\w+)\s*(?:\[(\w+)\])?\s*", decl).groups()
+            if length is not None and not length.isdigit():
+                length = re.search(rf"#define\s+{length}\s+(\d+)", src).group(1)
+            out.append((field, base, bool(star), None if length is None else int(length)))
+    return out
+
+
+SCALARS = {"double": ctypes.c_double, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+           "uint32_t": ctypes.c_uint32, "int": ctypes.c_int}
+
+
+def native_mirrors():
+    """{header struct: ctypes mirror} of every Structure in _native whose docstring names its header struct."""
+    out = {}
+    for obj in vars(_native).values():
+        if isinstance(obj, type) and issubclass(obj, ctypes.Structure) and obj is not ctypes.Structure:
+            m = re.match(r"(sst_\w+) \(include/sst\.h\)", obj.__doc__ or "")
+            if m:
+                out[m.group(1)] = obj
+    return out
+
+
+def test_mirrors_cover_the_stage_structs():
+    assert {"sst_row_slots", "sst_classify_args", "sst_fix_args", "sst_bins_args", "sst_dict_args",
+            "sst_length_queries", "sst_walk_args", "sst_handoff_args", "sst_exact_io"} <= set(native_mirrors())
+
+
+@pytest.mark.parametrize("name", sorted(native_mirrors()))
+def test_ctypes_mirror_matches_header_struct(name):
+    """The mirror has the header struct's fields, in its order, each of the
+    header's kind: any pointer a c_void_p, a scalar its ctypes twin, T x[N]
+    an array of N of them."""
+    want = []
+    for field, base, pointer, length in header_struct_fields(name):
+        kind = ctypes.c_void_p if pointer else SCALARS[base]
+        want.append((field, kind if length is None else kind * length))
+    assert [(n, t) for n, t, *_ in native_mirrors()[name]._fields_] == want
+    if name == "sst_walk_args":  # the array fields are seen
+        assert ("rq_block", ctypes.c_void_p * 16) in want
+
+
 def test_no_cpu_fallback_without_device():
     lib = _native.load_library()
     if lib.sst_device_count() > 0:
