@@ -1209,6 +1209,108 @@ int sst_align_windows_keep_device(sst_table* t, const sst_align_args* a, const s
 int sst_align_split_keep_device(sst_table* t, const sst_align_args* a, const sst_align_caps* caps,
                                 const sst_align_keep* keep);
 
+/* The final program: the optimal sequence by exact enumeration.  After
+ * filter_with_lp, Predictor.predict builds one LinearProgramInstance over the
+ * fragments that are left and reads the prediction from its solution
+ * (prediction.py:158-166; linear_program.py:164-225 the program, :238-313
+ * evaluate).  Here that program is enumerated, not solved.
+ * Per spectrum everything is as sst_align_windows_keep_device defines it: L,
+ * the position sets A_i (row 0 excluded), row_mod, mod_cap, row_cap, the
+ * admissible intervals per fragment class, the row-free test.
+ *   Used fragments: frag_use, one byte per fragment, NULL = all.  Only used
+ *     fragments enter the program.
+ *   Assignments: y takes one row of A_i per position.  y is feasible iff at
+ *     most mod_cap[g] of its rows have row_mod == 1.  combos = prod |A_i|,
+ *     saturating at UINT64_MAX; n_feas is the number of feasible y.  Order:
+ *     the index of y in mixed radix, position 0 most significant, rows
+ *     ascending within a position: index order is lexicographic order.
+ *   Fixed-point mass: u = su / prec in f64, qfix = (int64) rint(u * 65536.0),
+ *     ties to even.
+ *   Cost: c_j(y) = min over the admissible (l, r) of |qfix_j - 65536 S_y(l, r)|,
+ *     S_y the sum of w_{y_i} over [l, r] and 0 for the empty interval;
+ *     obj(y) = sum of c_j(y) over the used fragments, as u64.
+ *   Status per spectrum:
+ *     SST_FINAL_NONE        no fragments (a default spectrum): nothing computed
+ *     SST_FINAL_SKIPPED     not modelled: L outside [0, 253]; pos_off[g + 1] -
+ *                           pos_off[g] != L; a used START-only or END-only
+ *                           fragment with mn or mx outside [0, L - 1]; a used
+ *                           fragment whose u is not finite or has |u| >= 2^32;
+ *                           more than 16 384 used fragments (below these limits
+ *                           every total stays below 2^63)
+ *     SST_FINAL_INFEASIBLE  an empty A_i, or n_feas == 0
+ *     SST_FINAL_NOT_FREE    not row-free: the per-row caps may bind, and they
+ *                           are not enumerated
+ *     SST_FINAL_TOO_LARGE   combos > max_combos (1 <= max_combos <=
+ *                           SST_FINAL_MAX_COMBOS = sst_final_max_combos())
+ *     SST_FINAL_SOLVED      the optimum was found
+ *     Precedence: NONE, SKIPPED, an empty A_i, NOT_FREE, TOO_LARGE, n_feas == 0.
+ *   Outputs per spectrum: status; combos (0 for NONE and SKIPPED); and, all 0
+ *     (gap: UINT64_MAX) unless SOLVED: n_feas; best = min obj over the feasible
+ *     y; n_opt, the feasible y with obj == best (u32, saturating); gap, the
+ *     smallest obj above best minus best, UINT64_MAX if there is none.
+ *   Per position (seq, [pos_off[n_spec]]): the row of the first optimal y in
+ *     the order above; 0 unless SOLVED.
+ *   Per fragment: iv, under that y the smallest l << 8 | r among the
+ *     minimisers of c_j, the empty interval last as 0xFFFF; 0xFFFE for an
+ *     unused fragment or a spectrum that is not SOLVED.  sum: that interval's
+ *     S_y (0 where iv is 0xFFFE).
+ *   Every output element is written on every call.
+ * What SOLVED proves.  In a row-free spectrum the feasible y are exactly the
+ * program's y (keep mode's argument).  For a fixed y the x_j are independent:
+ * contiguity plus _set_x's fixings give exactly the admissible intervals.
+ * |qfix / 65536 - su / prec| < 2^-16 per fragment (rint, and one f64 division
+ * at |u| < 2^32), so obj / 65536 * prec is within n_used * 2^-16 * prec of the
+ * real objective of y's best x.  Hence if n_opt == 1 and gap > 2 n_used, the
+ * program's optimal y is unique in real arithmetic and is seq.  The claim holds
+ * for a solve run to optimality; a time-limited solve may return anything.  iv
+ * is AN optimal x: where two intervals tie, the reference's left / right and
+ * the sign of predicted_diff are the solver's choice.  n_opt > 1 (rows of equal
+ * mass, positions no fragment's best interval covers) is reported, not
+ * resolved.  No solver runs in this project: the claim is proven and held to a
+ * brute force, not solved.
+ * One kernel (k_final_program, sst_final.hip: one spectrum per workgroup, lanes
+ * over the indices of y) on the ctx stream; device pointers; no scratch buffer
+ * beyond the outputs, no global atomics.  SST_E_ARG with a message for a NULL
+ * struct or, with n_spec > 0, a NULL member (frag_use excepted); max_combos of
+ * 0 or above the limit; a non-positive or non-finite prec; and the row-mass
+ * limits of the align calls.  n_spec == 0 is SST_OK. */
+#define SST_FINAL_MAX_COMBOS (1ull << 22)
+#define SST_FINAL_NONE 0
+#define SST_FINAL_SOLVED 1
+#define SST_FINAL_TOO_LARGE 2
+#define SST_FINAL_INFEASIBLE 3
+#define SST_FINAL_SKIPPED 4
+#define SST_FINAL_NOT_FREE 5
+typedef struct sst_final_args {
+  int64_t n_spec;
+  const int32_t* seq_len;       /* [n_spec] */
+  const int64_t* pos_off;       /* [n_spec + 1] */
+  const uint64_t* skeleton;     /* [2 pos_off[n_spec]] */
+  const uint64_t* alpha;        /* [2 n_spec] */
+  const int64_t* frag_off;      /* [n_spec + 1] */
+  const uint8_t* frag_code;     /* [frag_off[n_spec]] each */
+  const double* frag_su;
+  const int32_t* frag_min_end;
+  const int32_t* frag_max_end;
+  const uint8_t* frag_use;      /* NULL: every fragment is used */
+  double prec;
+  const uint8_t* row_mod;       /* [table rows] */
+  const int32_t* mod_cap;       /* [n_spec] */
+  const int32_t* row_cap;       /* [254 * table rows] */
+  uint64_t max_combos;
+  uint8_t* status;              /* outputs, [n_spec] each */
+  uint64_t* combos;
+  uint64_t* n_feas;
+  uint64_t* best;
+  uint32_t* n_opt;
+  uint64_t* gap;
+  uint8_t* seq;                 /* [pos_off[n_spec]] */
+  uint16_t* iv;                 /* [frag_off[n_spec]] */
+  uint32_t* sum;                /* [frag_off[n_spec]] */
+} sst_final_args;
+uint64_t sst_final_max_combos(void);
+int sst_final_program_device(sst_table* t, const sst_final_args* a);
+
 /* compute_sequence_length_bound (mass_table.py:343-487) after the skeleton's
  * alphabet reduction (skeleton_building.py:315-336), both directions, for
  * queries on per-spectrum reduced alphabets, exact without a table rebuild:
@@ -1343,7 +1445,8 @@ int64_t sst_pyset_order(const int32_t* keys, const int64_t* hashes, int64_t n, i
 #define SST_K_ALIGN_SPLIT_CAPS 24 /* k_align_split_caps (sst_align_split_caps_device) */
 #define SST_K_ALIGN_KEEP 25 /* k_align_windows_keep (sst_align_windows_keep_device) */
 #define SST_K_ALIGN_SPLIT_KEEP 26 /* k_align_split_keep (sst_align_split_keep_device) */
-#define SST_K_COUNT 27
+#define SST_K_FINAL 27 /* k_final_program (sst_final_program_device) */
+#define SST_K_COUNT 28
 /* When enabled, every kernel launch of this ctx is bracketed by hipEvents
  * recorded on the ctx stream; sst_profile_read synchronises and returns the
  * summed milliseconds and launch counts per kernel id since the last read

@@ -42,6 +42,7 @@ EXPORTS = (
     "sst_align_capacity", "sst_align_windows_device", "sst_align_split_device",
     "sst_align_windows_caps_device", "sst_align_split_caps_device",
     "sst_align_windows_keep_device", "sst_align_split_keep_device",
+    "sst_final_max_combos", "sst_final_program_device",
 )
 
 # kernel ids of sst_profile_read
@@ -56,7 +57,8 @@ K_ALIGN_CAPS = 23
 K_ALIGN_SPLIT_CAPS = 24
 K_ALIGN_KEEP = 25
 K_ALIGN_SPLIT_KEEP = 26
-K_COUNT = 27  # SST_K_COUNT
+K_FINAL = 27
+K_COUNT = 28  # SST_K_COUNT
 KERNEL_NAMES = {K_IS_VALID: "k_is_valid", K_EXPLAIN_SCAN: "k_explain_scan", K_EXPLAIN_DEEP: "k_explain_deferred",
                 K_EXPLAIN_EXPAND: "k_explain_expand",
                 K_RESULT_PACK: "k_result_pack",  # ids 3, 4: reserved (merged into the deferred launch)
@@ -67,7 +69,7 @@ KERNEL_NAMES = {K_IS_VALID: "k_is_valid", K_EXPLAIN_SCAN: "k_explain_scan", K_EX
                 K_HANDOFF: "k_handoff", K_TABLE_CERTIFY: "k_table_certify", K_ALIGN: "k_align_windows",
                 K_ALIGN_SPLIT: "k_align_split", K_ALIGN_CAPS: "k_align_windows_caps",
                 K_ALIGN_SPLIT_CAPS: "k_align_split_caps", K_ALIGN_KEEP: "k_align_windows_keep",
-                K_ALIGN_SPLIT_KEEP: "k_align_split_keep"}
+                K_ALIGN_SPLIT_KEEP: "k_align_split_keep", K_FINAL: "k_final_program"}
 
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
@@ -183,6 +185,21 @@ class AlignKeep(ctypes.Structure):
 
 # sst_align_windows_device's status per fragment (SST_ALIGN_*)
 ALIGN_NONE, ALIGN_FIT, ALIGN_OPEN, ALIGN_INFEASIBLE, ALIGN_SKIPPED = range(5)
+
+
+class FinalArgs(ctypes.Structure):
+    """sst_final_args (include/sst.h): the final program over the hand-off's dense arrays (device pointers)."""
+    _fields_ = [("n_spec", ctypes.c_int64)] + \
+        [(n, ctypes.c_void_p) for n in ("seq_len", "pos_off", "skeleton", "alpha", "frag_off", "frag_code", "frag_su",
+                                        "frag_min_end", "frag_max_end", "frag_use")] + \
+        [("prec", ctypes.c_double)] + \
+        [(n, ctypes.c_void_p) for n in ("row_mod", "mod_cap", "row_cap")] + \
+        [("max_combos", ctypes.c_uint64)] + \
+        [(n, ctypes.c_void_p) for n in ("status", "combos", "n_feas", "best", "n_opt", "gap", "seq", "iv", "sum")]
+
+
+# sst_final_program_device's status per spectrum (SST_FINAL_*)
+FINAL_NONE, FINAL_SOLVED, FINAL_TOO_LARGE, FINAL_INFEASIBLE, FINAL_SKIPPED, FINAL_NOT_FREE = range(6)
 
 
 class RequeryMergeArgs(ctypes.Structure):
@@ -398,6 +415,10 @@ def load_library(path=LIB_PATH):
     for f in (lib.sst_align_windows_keep_device, lib.sst_align_split_keep_device):
         f.argtypes = [_P, ctypes.POINTER(AlignArgs), ctypes.POINTER(AlignCaps), ctypes.POINTER(AlignKeep)]
         f.restype = _I
+    lib.sst_final_max_combos.argtypes = []
+    lib.sst_final_max_combos.restype = _U64
+    lib.sst_final_program_device.argtypes = [_P, ctypes.POINTER(FinalArgs)]
+    lib.sst_final_program_device.restype = _I
     lib.sst_jaccard_device.argtypes = [_P, ctypes.POINTER(JaccardArgs)]
     lib.sst_jaccard_device.restype = _I
     lib.sst_skeleton_alpha_device.argtypes = [_P, _I64, _P, _P, _P, _P, _P]

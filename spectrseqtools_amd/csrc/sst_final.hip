@@ -1,0 +1,532 @@
+// sst_final.hip -- the final program by exact enumeration (gfx950): the optimal
+// sequence of a spectrum, the question Predictor.predict asks its last solver
+// call (prediction.py:158-166: LinearProgramInstance(...).evaluate,
+// linear_program.py:164-225 the program, :238-313 its reading).  The definition
+// is in include/sst.h (sst_final_program_device).
+//
+// For a fixed y (one row per position) the program decomposes: every fragment
+// independently takes the admissible interval whose sum is nearest to its
+// mass.  So the optimum is a minimum over y of a sum of per-fragment minima,
+// and k_final_program enumerates y: one spectrum per workgroup, persistent grid
+// with static striding over the spectra, lanes over the mixed-radix indices of y.
+//
+// Prologue per spectrum (LDS): one scan of the fragments for the conditions
+// that make the spectrum SKIPPED; per position |A_i| and its first row; thread 0
+// then walks the positions once: the prefix sums Pbase(i) with every free
+// position (|A_i| > 1) at its first row, k(i) = the free positions before i, the
+// free positions' radices and, per digit, the row, its mass above the first
+// row's (mod 2^32: the true prefix sums are below 2^32) and whether it is
+// modified; combos = prod |A_i|, saturating.  At most 22 free positions and 512
+// table entries are recorded: beyond either combos > 2^22 >= max_combos (radices
+// are in [2, 127], and x <= 18.2 log2(x) there, so radices of product <= 2^22 sum
+// to <= 400).  Then the row-free test, one row per thread, as keep mode's.
+//
+// A lane decodes its index (least significant digit = last free position) into
+// D[k][lane], k = 0 .. free positions: the digits' masses summed over the first
+// k free positions, so that P(i) = Pbase(i) + D[k(i)][lane] is the prefix sum of
+// its y (Pbase and k are shared, D is [k][lane]: a lane's column stays in one
+// bank whatever k it reads).  It counts the modified rows and skips y above
+// mod_cap.  The fragment records (qfix, class, ends) are held in LDS in chunks of
+// kFinalF; a lane keeps its partial objective across the chunks of one pass (a
+// spectrum of one chunk loads it once).  Terminal fragments walk their range of
+// ends, START_END takes the total, an internal fragment is a two-pointer sweep
+// over the non-decreasing prefix sums (O(L), the empty interval included: i == j).
+// Every lane keeps (best, the smallest objective above it, count, first index,
+// feasible count) and stops summing a y once its partial objective is above
+// both (costs only add, so that y changes none of them, nor the workgroup's);
+// the workgroup reduces the lanes' records by a tree in LDS.  Nothing in the
+// result depends on the order of the reduction: identical calls give identical
+// arrays.
+//
+// Epilogue: every lane decodes the winner (the same D in every column), threads
+// over positions write seq, threads over fragments walk the admissible intervals
+// in (l, r) order for iv and sum.  Every global store is a plain vector store of
+// an output element; no global atomics, no scratch buffer.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "sst_internal.h"
+
+namespace sst {
+
+namespace {
+
+constexpr int kFinalWG = 256;
+constexpr int kFinalF = 512;        // fragment records per chunk
+constexpr int kFinalMaxLen = 253;   // as the alignment certificate
+constexpr int kFinalMaxFree = 22;   // free positions of a spectrum of at most 2^22 assignments
+constexpr int kFinalTable = 512;    // digits of all free positions together
+constexpr uint32_t kFinalMaxUsed = 16384;
+constexpr uint64_t kNone64 = ~0ull;
+static_assert(SST_FINAL_MAX_COMBOS == 1ull << kFinalMaxFree, "every free position has at least two rows");
+
+struct FinalLds {
+  uint32_t D[kFinalMaxFree + 1][kFinalWG];  // per lane: its digits' masses over the first k free positions
+  unsigned long long r_best[kFinalWG];      // the reduction
+  unsigned long long r_next[kFinalWG];
+  uint32_t r_count[kFinalWG];
+  uint32_t r_first[kFinalWG];
+  uint32_t r_feas[kFinalWG];
+  int64_t f_q[kFinalF];         // a chunk's records: qfix
+  uint32_t f_meta[kFinalF];     // class | unused << 2 | first end << 8 | last end << 16
+  uint32_t pbase[256];          // P(i) with every free position at its first row, i in [0, L]
+  uint32_t w[SST_MAX_ROWS + 8];
+  uint32_t t_delta[kFinalTable];  // per digit of a free position: its row's mass above the first row's (mod 2^32)
+  uint8_t t_row[kFinalTable];
+  uint8_t t_mod[kFinalTable];
+  uint16_t f_off[kFinalMaxFree + 2];  // a free position's first digit in the table
+  uint8_t f_radix[kFinalMaxFree + 2];
+  uint8_t kof[256];             // free positions before position i, i in [0, L]
+  uint8_t p_cnt[256];           // |A_i|, and its first row
+  uint8_t p_first[256];
+  uint8_t w_digit[kFinalMaxFree + 2];  // the winner's digits
+  unsigned long long mod[2];    // the table's modified rows
+  unsigned long long combos;
+  uint32_t flags;               // 1: an empty A_i; 2: a SKIPPED condition among the used fragments; 4: a row is not free
+  uint32_t n_used;
+  uint32_t n_free;
+  int32_t fixed_mod;            // modified rows among the positions of one row
+};
+static_assert(sizeof(FinalLds) <= 64 * 1024, "static LDS");
+
+struct FinalKArgs {
+  sst_final_args a;
+  const int* w;
+  int n_rows;
+};
+
+// A_i of position p: P_i & alpha where P_i != 0, else alpha; row 0 excluded (a0 / a1 hold rows 1 .. n_rows - 1 only)
+__device__ __forceinline__ void final_set(const uint64_t* skel, uint64_t a0, uint64_t a1, int p, uint64_t& m0,
+                                          uint64_t& m1) {
+  const uint64_t p0 = skel[2 * p], p1 = skel[2 * p + 1];
+  if (p0 | p1) {
+    m0 = p0 & a0;
+    m1 = p1 & a1;
+  } else {
+    m0 = a0;
+    m1 = a1;
+  }
+}
+
+// qfix of a fragment; false where the model does not hold (u not finite or |u| >= 2^32)
+__device__ __forceinline__ bool final_qfix(double su, double prec, int64_t& q) {
+  const double u = su / prec;
+  if (!(__builtin_fabs(u) < 0x1p32)) return false;  // (NaN and the infinities fail the comparison)
+  q = (int64_t)__builtin_rint(u * 65536.0);
+  return true;
+}
+
+// class and range of ends of a fragment, as a record's meta word; false: a terminal fragment with an end outside [0, L - 1]
+__device__ __forceinline__ bool final_meta(uint8_t code, int mn, int mx, int L, uint32_t& meta) {
+  const uint32_t cls = (code >> 2) & 3u;
+  meta = cls;
+  if (cls == 1 || cls == 2) {
+    if (mn < 0 || mn >= L || mx < 0 || mx >= L) return false;
+    const int lo = mn < mx ? mn : mx, hi = cls == 1 ? mx : mn;
+    meta |= (uint32_t)lo << 8 | (uint32_t)hi << 16;
+  }
+  return true;
+}
+
+__device__ __forceinline__ uint32_t final_prefix(const FinalLds& s, int i, int tid) {
+  return s.pbase[i] + s.D[s.kof[i]][tid];
+}
+
+__device__ __forceinline__ uint64_t final_dist(int64_t q, uint32_t sum) {
+  const int64_t d = q - (int64_t)((uint64_t)sum << 16);
+  return (uint64_t)(d < 0 ? -d : d);
+}
+
+// c_j(y) of the lane's y
+__device__ __forceinline__ uint64_t final_cost(const FinalLds& s, int64_t q, uint32_t meta, int L, int tid) {
+  const uint32_t cls = meta & 3u;
+  const int lo = (int)((meta >> 8) & 0xffu), hi = (int)((meta >> 16) & 0xffu);
+  if (cls == 3) return final_dist(q, final_prefix(s, L, tid));
+  uint64_t best = kNone64;
+  if (cls == 1) {
+    for (int r = lo; r <= hi; ++r) {
+      const uint64_t c = final_dist(q, final_prefix(s, r + 1, tid));
+      best = c < best ? c : best;
+    }
+    return best;
+  }
+  if (cls == 2) {
+    const uint32_t total = final_prefix(s, L, tid);
+    for (int l = lo; l <= hi; ++l) {
+      const uint64_t c = final_dist(q, total - final_prefix(s, l, tid));
+      best = c < best ? c : best;
+    }
+    return best;
+  }
+  if (q <= 0) return (uint64_t)(-q);  // every sum is >= 0: the empty interval
+  // i <= j over P(0 .. L): the sum P(j) - P(i) grows with j and falls with i; the pointer that can still improve moves
+  int i = 0, j = 0;
+  uint32_t pi = final_prefix(s, 0, tid), pj = pi;
+  for (;;) {
+    const int64_t d = q - (int64_t)((uint64_t)(pj - pi) << 16);
+    const uint64_t c = (uint64_t)(d < 0 ? -d : d);
+    best = c < best ? c : best;
+    if (d > 0) {
+      if (j == L) break;
+      pj = final_prefix(s, ++j, tid);
+    } else {
+      if (d == 0) break;
+      pi = final_prefix(s, ++i, tid);  // (d < 0 only where i < j, as q > 0)
+    }
+  }
+  return best;
+}
+
+// The lane's column of D from the index of a y; returns its modified rows among the free positions.  w_digit: the
+// digits are also written there (the winner, by one thread).
+__device__ __forceinline__ int final_decode(FinalLds& s, uint32_t idx, int n_free, int tid, bool digits) {
+  int mods = 0;
+  uint32_t rem = idx;
+  for (int f = n_free - 1; f >= 0; --f) {
+    const uint32_t radix = s.f_radix[f], d = rem % radix;
+    rem /= radix;
+    const int e = (int)s.f_off[f] + (int)d;
+    s.D[f + 1][tid] = s.t_delta[e];
+    mods += s.t_mod[e];
+    if (digits) s.w_digit[f] = (uint8_t)d;
+  }
+  uint32_t acc = 0;
+  s.D[0][tid] = 0;
+  for (int f = 0; f < n_free; ++f) {
+    acc += s.D[f + 1][tid];
+    s.D[f + 1][tid] = acc;
+  }
+  return mods;
+}
+
+// A spectrum that is not SOLVED: its per-spectrum outputs and the defaults of its positions and fragments.
+__device__ __forceinline__ void final_write_unsolved(const sst_final_args& a, int64_t g, uint8_t status, uint64_t combos,
+                                                     int64_t pos0, int64_t n_pos, int64_t f0, int64_t nf_all, int tid) {
+  if (tid == 0) {
+    a.status[g] = status;
+    a.combos[g] = combos;
+    a.n_feas[g] = 0;
+    a.best[g] = 0;
+    a.n_opt[g] = 0;
+    a.gap[g] = kNone64;
+  }
+  for (int64_t p = tid; p < n_pos; p += kFinalWG) a.seq[pos0 + p] = 0;
+  for (int64_t j = tid; j < nf_all; j += kFinalWG) {
+    a.iv[f0 + j] = 0xFFFE;
+    a.sum[f0 + j] = 0;
+  }
+}
+
+__global__ __launch_bounds__(kFinalWG) void k_final_program(FinalKArgs k) {
+  __shared__ FinalLds s;
+  const sst_final_args& a = k.a;
+  const int tid = (int)threadIdx.x;
+
+  for (int r = tid; r < SST_MAX_ROWS + 8; r += kFinalWG) s.w[r] = r < k.n_rows ? (uint32_t)k.w[r] : 0u;
+  uint64_t rows0 = ~1ull, rows1 = ~0ull;
+  if (k.n_rows < 64) {
+    rows0 &= (1ull << k.n_rows) - 1;
+    rows1 = 0;
+  } else if (k.n_rows < 128) {
+    rows1 = (1ull << (k.n_rows - 64)) - 1;
+  }
+  if (tid < 2) s.mod[tid] = 0;
+  __syncthreads();
+  for (int r = 1 + tid; r < k.n_rows && r < 128; r += kFinalWG)
+    if (a.row_mod[r]) atomicOr(&s.mod[r >> 6], 1ull << (r & 63));
+  __syncthreads();
+  const uint64_t mod0 = s.mod[0], mod1 = s.mod[1];
+
+  for (int64_t g = blockIdx.x; g < a.n_spec; g += gridDim.x) {
+    const int64_t f0 = a.frag_off[g], nf_all = a.frag_off[g + 1] - f0;
+    const int64_t pos0 = a.pos_off[g], n_pos = a.pos_off[g + 1] - pos0;
+    if (nf_all <= 0) {  // a default spectrum, or one without fragments: nothing is computed
+      final_write_unsolved(a, g, SST_FINAL_NONE, 0, pos0, n_pos, f0, 0, tid);
+      continue;
+    }
+    const int L = a.seq_len[g];
+    if (!(L >= 0 && L <= kFinalMaxLen && n_pos == (int64_t)L)) {
+      final_write_unsolved(a, g, SST_FINAL_SKIPPED, 0, pos0, n_pos, f0, nf_all, tid);
+      continue;
+    }
+    const uint64_t* skel = a.skeleton + 2 * pos0;
+    const uint64_t a0 = a.alpha[2 * g] & rows0, a1 = a.alpha[2 * g + 1] & rows1;
+    const int mod_cap = a.mod_cap[g];
+    __syncthreads();  // the previous spectrum's LDS is no longer read
+    if (tid == 0) {
+      s.flags = 0;
+      s.n_used = 0;
+    }
+    __syncthreads();
+
+    // the used fragments: their number, and the conditions the model does not hold under
+    {
+      uint32_t used = 0;
+      bool bad = false;
+      for (int64_t j = tid; j < nf_all; j += kFinalWG) {
+        const int64_t at = f0 + j;
+        if (a.frag_use && !a.frag_use[at]) continue;
+        ++used;
+        int64_t q;
+        uint32_t meta;
+        bad = bad || !final_qfix(a.frag_su[at], a.prec, q) ||
+              !final_meta(a.frag_code[at], a.frag_min_end[at], a.frag_max_end[at], L, meta);
+      }
+      if (used) atomicAdd(&s.n_used, used);
+      if (bad) atomicOr(&s.flags, 2u);
+    }
+    for (int p = tid; p < L; p += kFinalWG) {
+      uint64_t m0, m1;
+      final_set(skel, a0, a1, p, m0, m1);
+      const int cnt = __builtin_popcountll(m0) + __builtin_popcountll(m1);
+      s.p_cnt[p] = (uint8_t)cnt;
+      s.p_first[p] = (uint8_t)(m0 ? __builtin_ctzll(m0) : m1 ? 64 + __builtin_ctzll(m1) : 0);
+      if (cnt == 0) atomicOr(&s.flags, 1u);
+    }
+    __syncthreads();
+    if ((s.flags & 2u) || s.n_used > kFinalMaxUsed) {
+      final_write_unsolved(a, g, SST_FINAL_SKIPPED, 0, pos0, n_pos, f0, nf_all, tid);
+      continue;
+    }
+    if (s.flags & 1u) {  // (combos = prod |A_i| = 0)
+      final_write_unsolved(a, g, SST_FINAL_INFEASIBLE, 0, pos0, n_pos, f0, nf_all, tid);
+      continue;
+    }
+
+    if (tid == 0) {  // one walk over the positions
+      uint64_t combos = 1;
+      uint32_t pre = 0;
+      int n_free = 0, t_n = 0, fixed_mod = 0;
+      bool over = false;  // more free positions or digits than are recorded: combos > 2^22
+      for (int p = 0; p < L; ++p) {
+        const int cnt = s.p_cnt[p], first = s.p_first[p];
+        s.pbase[p] = pre;
+        s.kof[p] = (uint8_t)n_free;
+        pre += s.w[first];
+        combos = combos > kNone64 / (uint64_t)cnt ? kNone64 : combos * (uint64_t)cnt;
+        if (cnt == 1) {
+          fixed_mod += (int)(((first < 64 ? mod0 : mod1) >> (first & 63)) & 1u);
+        } else if (!over) {
+          if (n_free == kFinalMaxFree || t_n + cnt > kFinalTable) {
+            over = true;
+            continue;
+          }
+          uint64_t m0, m1;
+          final_set(skel, a0, a1, p, m0, m1);
+          s.f_off[n_free] = (uint16_t)t_n;
+          s.f_radix[n_free] = (uint8_t)cnt;
+          for (int h = 0; h < 2; ++h)
+            for (uint64_t m = h ? m1 : m0; m; m &= m - 1) {
+              const int bit = __builtin_ctzll(m), row = 64 * h + bit;
+              s.t_delta[t_n] = s.w[row] - s.w[first];
+              s.t_row[t_n] = (uint8_t)row;
+              s.t_mod[t_n] = (uint8_t)(((h ? mod1 : mod0) >> bit) & 1u);
+              ++t_n;
+            }
+          ++n_free;
+        }
+      }
+      s.pbase[L] = pre;
+      s.kof[L] = (uint8_t)n_free;
+      s.combos = combos;
+      s.n_free = (uint32_t)n_free;
+      s.fixed_mod = fixed_mod;
+    }
+    // the row-free test: one row of alpha per thread, n_r counted over the positions' sets
+    for (int r = 1 + tid; r < k.n_rows; r += kFinalWG) {
+      const uint64_t bit = 1ull << (r & 63);
+      if (!((r < 64 ? a0 : a1) & bit)) continue;
+      int n_r = 0;
+      for (int p = 0; p < L; ++p) {
+        uint64_t m0, m1;
+        final_set(skel, a0, a1, p, m0, m1);
+        n_r += ((r < 64 ? m0 : m1) & bit) != 0;
+      }
+      const int cap = a.row_cap[(int64_t)L * k.n_rows + r];
+      const bool modified = ((r < 64 ? mod0 : mod1) & bit) != 0;
+      if (!(cap >= n_r || (modified && cap >= mod_cap))) atomicOr(&s.flags, 4u);
+    }
+    __syncthreads();
+    const uint64_t combos = s.combos;
+    if (s.flags & 4u) {
+      final_write_unsolved(a, g, SST_FINAL_NOT_FREE, combos, pos0, n_pos, f0, nf_all, tid);
+      continue;
+    }
+    if (combos > a.max_combos) {
+      final_write_unsolved(a, g, SST_FINAL_TOO_LARGE, combos, pos0, n_pos, f0, nf_all, tid);
+      continue;
+    }
+
+    // the enumeration: combos <= 2^22, every free position is recorded
+    const int n_free = (int)s.n_free, fixed_mod = s.fixed_mod;
+    const int n_chunks = (int)((nf_all + kFinalF - 1) / kFinalF);
+    uint64_t best = kNone64, next = kNone64;
+    uint32_t count = 0, first_at = 0, feas = 0;
+    for (uint32_t base = 0; base < (uint32_t)combos; base += kFinalWG) {
+      const uint32_t idx = base + (uint32_t)tid;
+      bool ok = idx < (uint32_t)combos;
+      if (ok) ok = fixed_mod + final_decode(s, idx, n_free, tid, false) <= mod_cap;
+      uint64_t obj = 0;
+      bool live = ok;  // the objective is still summed
+      for (int c = n_chunks - 1; c >= 0; --c) {  // (the last fragments first: see below)
+        const int nf = (int)(nf_all - (int64_t)c * kFinalF < kFinalF ? nf_all - (int64_t)c * kFinalF : kFinalF);
+        if (n_chunks > 1 || base == 0) {
+          __syncthreads();  // the previous chunk's records are no longer read
+          for (int j = tid; j < nf; j += kFinalWG) {
+            const int64_t at = f0 + (int64_t)c * kFinalF + j;
+            int64_t q = 0;
+            uint32_t meta = 4u;
+            if (!a.frag_use || a.frag_use[at]) {  // (a used fragment is within the model: checked above)
+              final_qfix(a.frag_su[at], a.prec, q);
+              final_meta(a.frag_code[at], a.frag_min_end[at], a.frag_max_end[at], L, meta);
+            }
+            s.f_q[j] = q;
+            s.f_meta[j] = meta;
+          }
+          __syncthreads();
+        }
+        // from the last record down: the hand-off's order is ascending su, and the heavy fragments tell the y apart
+        if (live)
+          for (int j = nf - 1; j >= 0 && live; --j) {
+            const uint32_t meta = s.f_meta[j];
+            if (meta & 4u) continue;
+            obj += final_cost(s, s.f_q[j], meta, L, tid);
+            live = obj <= next;  // costs only add: above the lane's two smallest objectives y changes no output
+          }
+      }
+      if (ok) ++feas;
+      if (live) {
+        if (obj < best) {
+          next = best;
+          best = obj;
+          count = 1;
+          first_at = idx;
+        } else if (obj == best) {
+          ++count;
+        } else if (obj < next) {
+          next = obj;
+        }
+      }
+    }
+    s.r_best[tid] = best;
+    s.r_next[tid] = next;
+    s.r_count[tid] = count;
+    s.r_first[tid] = first_at;
+    s.r_feas[tid] = feas;
+    __syncthreads();
+    for (int stride = kFinalWG / 2; stride > 0; stride >>= 1) {
+      if (tid < stride) {
+        const uint64_t b1 = s.r_best[tid], b2 = s.r_best[tid + stride];
+        const uint64_t n1 = s.r_next[tid], n2 = s.r_next[tid + stride];
+        const uint32_t i1 = s.r_first[tid], i2 = s.r_first[tid + stride];
+        s.r_feas[tid] += s.r_feas[tid + stride];
+        if (b1 == b2) {
+          s.r_next[tid] = n1 < n2 ? n1 : n2;
+          s.r_count[tid] += s.r_count[tid + stride];
+          s.r_first[tid] = i1 < i2 ? i1 : i2;
+        } else if (b1 < b2) {
+          s.r_next[tid] = n1 < b2 ? n1 : b2;
+        } else {
+          s.r_best[tid] = b2;
+          s.r_next[tid] = n2 < b1 ? n2 : b1;
+          s.r_count[tid] = s.r_count[tid + stride];
+          s.r_first[tid] = i2;
+        }
+      }
+      __syncthreads();
+    }
+    const uint32_t n_feas = s.r_feas[0];
+    if (n_feas == 0) {
+      final_write_unsolved(a, g, SST_FINAL_INFEASIBLE, combos, pos0, n_pos, f0, nf_all, tid);
+      continue;
+    }
+    const uint32_t winner = s.r_first[0];
+    if (tid == 0) {
+      a.status[g] = SST_FINAL_SOLVED;
+      a.combos[g] = combos;
+      a.n_feas[g] = n_feas;
+      a.best[g] = s.r_best[0];
+      a.n_opt[g] = s.r_count[0];
+      a.gap[g] = s.r_next[0] == kNone64 ? kNone64 : s.r_next[0] - s.r_best[0];
+    }
+    // the winner again: every lane's column holds its D
+    final_decode(s, winner, n_free, tid, tid == 0);
+    __syncthreads();
+    for (int p = tid; p < L; p += kFinalWG) {
+      const int f = s.kof[p];
+      a.seq[pos0 + p] = s.p_cnt[p] == 1 ? s.p_first[p] : s.t_row[(int)s.f_off[f] + (int)s.w_digit[f]];
+    }
+    for (int64_t j = tid; j < nf_all; j += kFinalWG) {
+      const int64_t at = f0 + j;
+      uint16_t iv = 0xFFFE;
+      uint32_t sum = 0;
+      if (!a.frag_use || a.frag_use[at]) {
+        int64_t q = 0;
+        uint32_t meta = 0;
+        final_qfix(a.frag_su[at], a.prec, q);
+        final_meta(a.frag_code[at], a.frag_min_end[at], a.frag_max_end[at], L, meta);
+        const uint32_t cls = meta & 3u;
+        const int lo = (int)((meta >> 8) & 0xffu), hi = (int)((meta >> 16) & 0xffu);
+        uint64_t c_best = kNone64;
+        // the admissible intervals in (l, r) order, the empty one last; a later one wins only where it is nearer
+        if (cls == 3) {
+          iv = L ? (uint16_t)(L - 1) : (uint16_t)0xFFFF;
+          sum = final_prefix(s, L, tid);
+        } else if (cls == 1) {
+          for (int r = lo; r <= hi; ++r) {
+            const uint32_t x = final_prefix(s, r + 1, tid);
+            const uint64_t c = final_dist(q, x);
+            if (c < c_best) {
+              c_best = c;
+              iv = (uint16_t)r;
+              sum = x;
+            }
+          }
+        } else if (cls == 2) {
+          const uint32_t total = final_prefix(s, L, tid);
+          for (int l = lo; l <= hi; ++l) {
+            const uint32_t x = total - final_prefix(s, l, tid);
+            const uint64_t c = final_dist(q, x);
+            if (c < c_best) {
+              c_best = c;
+              iv = (uint16_t)(l << 8 | (L - 1));
+              sum = x;
+            }
+          }
+        } else {
+          for (int l = 0; l < L; ++l) {
+            const uint32_t pl = final_prefix(s, l, tid);
+            for (int r = l; r < L; ++r) {
+              const uint32_t x = final_prefix(s, r + 1, tid) - pl;
+              const uint64_t c = final_dist(q, x);
+              if (c < c_best) {
+                c_best = c;
+                iv = (uint16_t)(l << 8 | r);
+                sum = x;
+              }
+              if ((int64_t)((uint64_t)x << 16) >= q) break;  // the sums of [l, r + 1 ..] are no nearer
+            }
+          }
+          if (final_dist(q, 0) < c_best) {
+            iv = 0xFFFF;
+            sum = 0;
+          }
+        }
+      }
+      a.iv[at] = iv;
+      a.sum[at] = sum;
+    }
+  }
+}
+
+}  // namespace
+
+hipError_t launch_final(const sst_final_args& a, const int* w, int n_rows, int n_wg, hipStream_t st) {
+  if (a.n_spec <= 0) return hipSuccess;
+  const FinalKArgs k{a, w, n_rows};
+  const unsigned grid = (unsigned)(a.n_spec < (int64_t)n_wg ? a.n_spec : (int64_t)n_wg);
+  hipLaunchKernelGGL(k_final_program, dim3(grid), dim3(kFinalWG), 0, st, k);
+  return hipGetLastError();
+}
+
+}  // namespace sst

@@ -1,0 +1,434 @@
+"""The final program by exact enumeration: the optimal sequence of a spectrum
+(include/sst.h, sst_final_program_device; DESIGN "The final program").
+
+After filter_with_lp, Predictor.predict builds one LinearProgramInstance over
+the fragments that are left and reads the prediction from its solution
+(prediction.py:158-166; linear_program.py:164-225 the program, :238-313
+evaluate).  For a fixed y (one row per position) that program decomposes: every
+fragment independently takes the admissible interval whose sum is nearest to
+its mass, so the optimum is a minimum over y of a sum of per-fragment minima.
+Where the spectrum is row-free (keep mode's test) and has at most max_combos
+assignments, that minimum is enumerated here, in 2^-16 fixed point.
+
+final_host is the definition in numpy, vectorised over y (the mirror for
+spectra run_batch routed to the host, and the model the tests hold the kernel
+to), final_device the kernel (csrc/sst_final.hip) over a whole outcome.
+final_use turns a keep-mode AlignOutcome into the fragments that enter the
+program (the KEEP ones) and the spectra that still hold an LP_SOLVE fragment:
+their fragment set is the solver's to decide, so they get FINAL_UNDECIDED and
+never reach the kernel.  final_decisions says where the enumeration's optimum
+is provably the program's (FINAL_TAKE) and where a solver still has to run
+(FINAL_SOLVE).  A solver stopped by its time limit may return anything; TAKE
+equals the reference under completed solves only.
+"""
+import ctypes
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _native
+from ._native import FINAL_INFEASIBLE, FINAL_NONE, FINAL_NOT_FREE, FINAL_SKIPPED, FINAL_SOLVED, FINAL_TOO_LARGE
+from .alignment import ALIGN_MAX_LEN, LP_KEEP, LP_SOLVE, _rows_of, lp_caps, lp_decisions, lp_row_caps, position_sets
+
+FINAL_UNDECIDED = 6                 # Python layer only: the spectrum holds an LP_SOLVE fragment
+FINAL_MAX_COMBOS = 1 << 22          # sst_final_max_combos()
+FINAL_DEFAULT_COMBOS = 1 << 20
+FINAL_MAX_USED = 16384              # used fragments of a modelled spectrum
+FIX = 65536                         # fixed-point units per precision unit
+EMPTY_INTERVAL = 0xFFFF
+NO_INTERVAL = 0xFFFE
+NO_GAP = np.uint64(0xFFFFFFFFFFFFFFFF)
+STATUS_NAMES = {FINAL_NONE: "NONE", FINAL_SOLVED: "SOLVED", FINAL_TOO_LARGE: "TOO_LARGE",
+                FINAL_INFEASIBLE: "INFEASIBLE", FINAL_SKIPPED: "SKIPPED", FINAL_NOT_FREE: "NOT_FREE",
+                FINAL_UNDECIDED: "UNDECIDED"}
+FINAL_SOLVE, FINAL_TAKE = 0, 1
+_HOST_BLOCK = 1 << 22               # elements of a block of interval sums (final_host)
+
+
+@dataclass
+class FinalOutcome:
+    """The final program's result per spectrum, position and fragment, parallel
+    to a BatchOutcome (position p of spectrum g at pos_off[g] + p, fragment k at
+    frag_off[g] + k), as host arrays."""
+    frag_off: np.ndarray  # [S + 1] i64, the BatchOutcome's
+    pos_off: np.ndarray   # [S + 1] i64, the BatchOutcome's
+    status: np.ndarray    # u8 FINAL_*
+    combos: np.ndarray    # u64 prod |A_i|, saturating
+    n_feas: np.ndarray    # u64 feasible y (0 unless SOLVED)
+    best: np.ndarray      # u64 min obj
+    n_opt: np.ndarray     # u32 feasible y with obj == best
+    gap: np.ndarray       # u64 smallest obj above best, minus best; NO_GAP if none
+    seq: np.ndarray       # u8 per position: the row of the first optimal y
+    iv: np.ndarray        # u16 per fragment: its interval under that y, NO_INTERVAL if unused / not SOLVED
+    sum: np.ndarray       # u32 per fragment: that interval's sum
+
+    SPECTRUM_FIELDS = ("status", "combos", "n_feas", "best", "n_opt", "gap")
+    FRAGMENT_FIELDS = ("iv", "sum")
+    _DTYPES = {"frag_off": np.int64, "pos_off": np.int64, "status": np.uint8, "combos": np.uint64, "n_feas": np.uint64,
+               "best": np.uint64, "n_opt": np.uint32, "gap": np.uint64, "seq": np.uint8, "iv": np.uint16,
+               "sum": np.uint32}
+
+    def __post_init__(self):
+        for k, dt in self._DTYPES.items():
+            setattr(self, k, np.ascontiguousarray(getattr(self, k), dtype=dt))
+        S = len(self.frag_off) - 1
+        if S < 0 or len(self.pos_off) != S + 1 or any(len(getattr(self, k)) != S for k in self.SPECTRUM_FIELDS) or \
+                len(self.seq) != int(self.pos_off[-1]) or \
+                any(len(getattr(self, k)) != int(self.frag_off[-1]) for k in self.FRAGMENT_FIELDS):
+            raise ValueError("FinalOutcome: arrays do not match frag_off / pos_off")
+
+    def __len__(self):
+        return len(self.frag_off) - 1
+
+    def equals(self, other):
+        return all(np.array_equal(getattr(self, k), getattr(other, k)) for k in self._DTYPES)
+
+    def shares(self):
+        """Share of each status over all spectra, by name."""
+        n = max(1, len(self.status))
+        return {name: float(np.count_nonzero(self.status == st)) / n for st, name in STATUS_NAMES.items()}
+
+    def n_used(self):
+        """Used fragments per spectrum (i64): those with an interval, so 0 where the spectrum is not SOLVED."""
+        used = np.concatenate([[0], np.cumsum(self.iv != NO_INTERVAL)])
+        return (used[self.frag_off[1:]] - used[self.frag_off[:-1]]).astype(np.int64)
+
+    def take(self, idx):
+        """The result of spectra idx, in that order (as BatchOutcome.take)."""
+        from .pipeline_device import _segments
+
+        idx = np.asarray(idx, dtype=np.int64)
+        fsrc, foff = _segments(self.frag_off, idx)
+        psrc, poff = _segments(self.pos_off, idx)
+        return FinalOutcome(frag_off=foff, pos_off=poff, seq=self.seq[psrc],
+                            **{k: getattr(self, k)[idx] for k in self.SPECTRUM_FIELDS},
+                            **{k: getattr(self, k)[fsrc] for k in self.FRAGMENT_FIELDS})
+
+    @classmethod
+    def concat(cls, outcomes):
+        """Several results' spectra one after the other (as BatchOutcome.concat)."""
+        outcomes = list(outcomes)
+        if not outcomes:
+            raise ValueError("FinalOutcome.concat: nothing to concatenate")
+
+        def offsets(name):
+            base = np.concatenate([[0], np.cumsum([int(getattr(o, name)[-1]) for o in outcomes])]).astype(np.int64)
+            return np.concatenate([getattr(o, name)[:-1] + b for o, b in zip(outcomes, base)] + [base[-1:]])
+
+        fields = cls.SPECTRUM_FIELDS + cls.FRAGMENT_FIELDS + ("seq",)
+        return cls(frag_off=offsets("frag_off"), pos_off=offsets("pos_off"),
+                   **{k: np.concatenate([getattr(o, k) for o in outcomes]) for k in fields})
+
+    @classmethod
+    def blank(cls, outcome, status=FINAL_NONE):
+        """Every spectrum of `outcome` with `status` and the outputs of a spectrum that is not SOLVED."""
+        S, nf, n_pos = len(outcome), int(outcome.frag_off[-1]), int(outcome.pos_off[-1])
+        return cls(frag_off=np.array(outcome.frag_off, dtype=np.int64), pos_off=np.array(outcome.pos_off, dtype=np.int64),
+                   status=np.full(S, status, np.uint8), combos=np.zeros(S, np.uint64), n_feas=np.zeros(S, np.uint64),
+                   best=np.zeros(S, np.uint64), n_opt=np.zeros(S, np.uint32), gap=np.full(S, NO_GAP, np.uint64),
+                   seq=np.zeros(n_pos, np.uint8), iv=np.full(nf, NO_INTERVAL, np.uint16), sum=np.zeros(nf, np.uint32))
+
+
+def final_use(al):
+    """(use, undecided) from a keep-mode AlignOutcome: use u8 per fragment, 1
+    for the LP_KEEP fragments (filter_with_lp, run to optimality, keeps exactly
+    those where nothing is LP_SOLVE); undecided bool per spectrum, True where
+    some fragment is LP_SOLVE: the final program's fragment set is then the
+    solver's to decide."""
+    if not al.has_keep:
+        raise ValueError("final_use: the AlignOutcome is not in keep mode")
+    dec = lp_decisions(al)
+    solve = np.concatenate([[0], np.cumsum(dec == LP_SOLVE)])
+    return (dec == LP_KEEP).astype(np.uint8), (solve[al.frag_off[1:]] - solve[al.frag_off[:-1]]) > 0
+
+
+def final_decisions(fo, min_gap_units=0.5):
+    """Per spectrum (u8) FINAL_TAKE where the enumeration's optimum is provably
+    the program's unique one with a margin: SOLVED, n_opt == 1 and gap >=
+    max(2 n_used + 1, min_gap_units * 65536) (the rounding of the fixed-point
+    masses moves every objective by less than n_used units; half a precision
+    unit is the margin of the DROP and KEEP sides); else FINAL_SOLVE."""
+    need = np.maximum(2 * fo.n_used() + 1, int(np.ceil(min_gap_units * FIX))).astype(np.uint64)
+    take = (fo.status == FINAL_SOLVED) & (fo.n_opt == 1) & (fo.gap >= need)
+    return np.where(take, FINAL_TAKE, FINAL_SOLVE).astype(np.uint8)
+
+
+def sequence_names(fo, outcome, g):
+    """The list of names evaluate (linear_program.py:249) would return for
+    spectrum g: the first name of the row at every position.  ValueError unless
+    the spectrum is SOLVED."""
+    if fo.status[g] != FINAL_SOLVED:
+        raise ValueError(f"sequence_names: spectrum {g} is {STATUS_NAMES[int(fo.status[g])]}, not SOLVED")
+    return [outcome.row_names[int(r)] for r in fo.seq[int(fo.pos_off[g]):int(fo.pos_off[g + 1])]]
+
+
+def _check_max_combos(max_combos, who):
+    max_combos = int(max_combos)
+    if not 1 <= max_combos <= FINAL_MAX_COMBOS:
+        raise ValueError(f"{who}: max_combos outside [1, 2^22]")
+    return max_combos
+
+
+def _per_fragment(use, nf, who):
+    if use is None:
+        return np.ones(nf, np.uint8)
+    use = (np.asarray(use).reshape(-1) != 0).astype(np.uint8)
+    if len(use) != nf:
+        raise ValueError(f"{who}: use does not match the outcome's fragments")
+    return use
+
+
+def _per_spectrum(undecided, S, who):
+    if undecided is None:
+        return np.zeros(S, bool)
+    undecided = np.asarray(undecided).reshape(-1) != 0
+    if len(undecided) != S:
+        raise ValueError(f"{who}: undecided does not match the outcome's spectra")
+    return undecided
+
+
+def _ends(cls, mn, mx):
+    """The range of ends a terminal fragment walks: r in [lo, hi] (START), l in [lo, hi] (END)."""
+    return min(mn, mx), (mx if cls == 1 else mn)
+
+
+def _solve_spectrum(L, sets, row_mass, row_mod, mod_cap, cls, qfix, mn, mx):
+    """The enumeration of one modelled, row-free spectrum within max_combos:
+    (n_feas, best, n_opt, gap, seq, iv, sum); n_feas == 0: no feasible y."""
+    radices = [len(rows) for rows in sets]
+    combos = int(np.prod(radices, dtype=object)) if L else 1
+    mass = [np.array([int(row_mass[r]) for r in rows], dtype=np.int64) for rows in sets]
+    mod = [np.array([int(row_mod[r] != 0) for r in rows], dtype=np.int64) for rows in sets]
+    ia, ib = np.triu_indices(L + 1, k=1)  # (a, b), a < b, in (a, b) order: the interval [a, b - 1] in (l, r) order
+    internal = np.flatnonzero(cls == 0)
+    block = max(1, _HOST_BLOCK // max(1, len(ia))) if len(internal) else 1 << 16
+    q = qfix.astype(np.int64)
+
+    def digits_of(idx):
+        """The mixed-radix digits of the indices idx, position 0 most significant: [n, L]"""
+        out = np.zeros((len(idx), L), np.int64)
+        rem = np.array(idx, dtype=np.int64)
+        for p in range(L - 1, -1, -1):
+            if radices[p] > 1:
+                rem, out[:, p] = np.divmod(rem, radices[p])
+        return out
+
+    def prefix_of(idx):
+        digits = digits_of(idx)
+        w = np.stack([mass[p][digits[:, p]] for p in range(L)], axis=1) if L else np.zeros((len(idx), 0), np.int64)
+        n_mod = sum((mod[p][digits[:, p]] for p in range(L)), np.zeros(len(idx), np.int64))
+        return np.concatenate([np.zeros((len(idx), 1), np.int64), np.cumsum(w, axis=1)], axis=1), n_mod
+
+    def costs(P, j, pairs):
+        """|qfix_j - 65536 S| over fragment j's admissible intervals, in (l, r) order, the empty one last: [n, n_iv]"""
+        if cls[j] == 3:
+            s = P[:, L:L + 1]
+        elif cls[j] == 1:
+            lo, hi = _ends(1, int(mn[j]), int(mx[j]))
+            s = P[:, lo + 1:hi + 2]
+        elif cls[j] == 2:
+            lo, hi = _ends(2, int(mn[j]), int(mx[j]))
+            s = P[:, L:L + 1] - P[:, lo:hi + 1]
+        else:
+            s = np.concatenate([pairs, np.zeros((len(P), 1), np.int64)], axis=1)
+        return np.abs(q[j] - FIX * s), s
+
+    n_feas, best, n_opt, nxt, first = 0, None, 0, None, -1
+    for start in range(0, combos, block):
+        idx = np.arange(start, min(combos, start + block), dtype=np.int64)
+        P, n_mod = prefix_of(idx)
+        ok = n_mod <= mod_cap
+        if not ok.any():
+            continue
+        P, idx = P[ok], idx[ok]
+        pairs = P[:, ib] - P[:, ia] if len(internal) else None
+        obj = np.zeros(len(idx), np.int64)
+        for j in range(len(cls)):
+            obj += costs(P, j, pairs)[0].min(axis=1)
+        n_feas += len(idx)
+        vals = np.unique(obj)
+        for v in vals[:2].tolist():  # the block's smallest two distinct objectives
+            if best is None or v < best:
+                best, nxt, n_opt, first = v, best, 0, -1
+            elif v != best and (nxt is None or v < nxt):
+                nxt = v
+        at = np.flatnonzero(obj == best)
+        if len(at):
+            n_opt += len(at)
+            if first < 0:
+                first = int(idx[at[0]])
+    if n_feas == 0:
+        return 0, 0, 0, NO_GAP, None, None, None
+    P, _ = prefix_of(np.array([first], dtype=np.int64))
+    seq = np.array([sets[p][int(d)] for p, d in enumerate(digits_of([first])[0])], dtype=np.uint8)
+    pairs = P[:, ib] - P[:, ia] if len(internal) else None
+    iv = np.empty(len(cls), np.uint16)
+    sm = np.empty(len(cls), np.uint32)
+    for j in range(len(cls)):
+        c, s = costs(P, j, pairs)
+        at = int(np.argmin(c[0]))  # the first minimiser: the smallest (l, r), the empty interval last
+        sm[j] = int(s[0, at])
+        if cls[j] == 3:
+            iv[j] = L - 1 if L else EMPTY_INTERVAL
+        elif cls[j] == 1:
+            iv[j] = _ends(1, int(mn[j]), int(mx[j]))[0] + at
+        elif cls[j] == 2:
+            iv[j] = (_ends(2, int(mn[j]), int(mx[j]))[0] + at) << 8 | (L - 1)
+        else:
+            iv[j] = EMPTY_INTERVAL if at == len(ia) else int(ia[at]) << 8 | (int(ib[at]) - 1)
+    return n_feas, best, min(n_opt, 0xFFFFFFFF), (NO_GAP if nxt is None else nxt - best), seq, iv, sm
+
+
+def final_host(outcome, precision, caps, row_cap, use=None, max_combos=FINAL_DEFAULT_COMBOS, undecided=None):
+    """The final program of every spectrum of `outcome` (a BatchOutcome) by the
+    definition (include/sst.h, sst_final_program_device), vectorised over y.
+    caps = (row_mod, mod_cap) (alignment.lp_caps), row_cap the per-row caps
+    table (alignment.lp_row_caps); use: u8 per fragment, None = all; undecided:
+    bool per spectrum, those get FINAL_UNDECIDED and nothing is computed."""
+    max_combos = _check_max_combos(max_combos, "final_host")
+    S, nf = len(outcome), int(outcome.frag_off[-1])
+    n_rows = len(outcome.row_mass)
+    row_mod = np.ascontiguousarray(caps[0], dtype=np.uint8)
+    mod_cap = np.ascontiguousarray(caps[1], dtype=np.int32)
+    if len(row_mod) != n_rows or len(mod_cap) != S:
+        raise ValueError("final_host: caps do not match the outcome's rows / spectra")
+    row_cap = np.ascontiguousarray(row_cap, dtype=np.int32).reshape(-1)
+    if len(row_cap) != (ALIGN_MAX_LEN + 1) * n_rows:
+        raise ValueError("final_host: row_cap is not a table of 254 lengths by the outcome's rows")
+    row_cap = row_cap.reshape(ALIGN_MAX_LEN + 1, n_rows)
+    if n_rows and (int(outcome.row_mass.min()) < 0 or int(outcome.row_mass.max()) >= (1 << 32) // ALIGN_MAX_LEN):
+        raise ValueError("final_host: a row mass outside [0, 2^32 / 253)")
+    use = _per_fragment(use, nf, "final_host")
+    undecided = _per_spectrum(undecided, S, "final_host")
+    fo = FinalOutcome.blank(outcome)
+    with np.errstate(all="ignore"):
+        u = np.asarray(outcome.frag_su, dtype=np.float64) / np.float64(precision)
+        in_model = np.abs(u) < 2.0 ** 32  # (False for NaN and the infinities)
+        qfix = np.where(in_model, np.rint(np.where(in_model, u, 0.0) * float(FIX)), 0.0).astype(np.int64)
+    cls_all = (np.asarray(outcome.frag_code).astype(np.int64) >> 2) & 3
+    for g in range(S):
+        if undecided[g]:
+            fo.status[g] = FINAL_UNDECIDED
+            continue
+        f = slice(int(outcome.frag_off[g]), int(outcome.frag_off[g + 1]))
+        if f.start == f.stop:
+            continue
+        L = int(outcome.seq_len[g])
+        p = slice(int(outcome.pos_off[g]), int(outcome.pos_off[g + 1]))
+        on = np.flatnonzero(use[f]) + f.start
+        cls = cls_all[on]
+        mn, mx = outcome.frag_min_end[on].astype(np.int64), outcome.frag_max_end[on].astype(np.int64)
+        terminal = (cls == 1) | (cls == 2)
+        if L < 0 or L > ALIGN_MAX_LEN or p.stop - p.start != L or len(on) > FINAL_MAX_USED or not in_model[on].all() or \
+                (terminal & ((mn < 0) | (mn >= L) | (mx < 0) | (mx >= L))).any():
+            fo.status[g] = FINAL_SKIPPED
+            continue
+        sets = position_sets(outcome.skeleton[p], outcome.alpha[g], n_rows)
+        combos = 1
+        for rows in sets:
+            combos *= len(rows)
+        fo.combos[g] = min(combos, (1 << 64) - 1)
+        if combos == 0:
+            fo.status[g] = FINAL_INFEASIBLE
+            continue
+        n_r = {}
+        for rows in sets:
+            for r in rows:
+                n_r[r] = n_r.get(r, 0) + 1
+        cap = int(mod_cap[g])
+        if not all(int(row_cap[L, r]) >= n_r.get(r, 0) or (row_mod[r] != 0 and int(row_cap[L, r]) >= cap)
+                   for r in _rows_of(int(outcome.alpha[g][0]), int(outcome.alpha[g][1]), n_rows)):
+            fo.status[g] = FINAL_NOT_FREE
+            continue
+        if combos > max_combos:
+            fo.status[g] = FINAL_TOO_LARGE
+            continue
+        n_feas, best, n_opt, gap, seq, iv, sm = _solve_spectrum(L, sets, outcome.row_mass, row_mod, cap, cls, qfix[on],
+                                                                mn, mx)
+        if n_feas == 0:
+            fo.status[g] = FINAL_INFEASIBLE
+            continue
+        fo.status[g], fo.n_feas[g], fo.best[g], fo.n_opt[g], fo.gap[g] = FINAL_SOLVED, n_feas, best, n_opt, gap
+        fo.seq[p], fo.iv[on], fo.sum[on] = seq, iv, sm
+    return fo
+
+
+def final_device(dp_table, outcome, use=None, max_combos=FINAL_DEFAULT_COMBOS, undecided=None, caps=None, row_cap=None):
+    """The final program of every spectrum of `outcome` on dp_table's device
+    (sst_final_program_device): one upload per input array, one launch, one
+    download per output array.  `outcome` must be on dp_table's rows.  caps and
+    row_cap default to alignment.lp_caps / lp_row_caps of the table; a (row_mod,
+    mod_cap) pair and a row_cap array are taken as they are.  use, undecided: as
+    final_host; undecided spectra are taken out before the upload."""
+    from .pipeline_device import _one_stream
+
+    max_combos = _check_max_combos(max_combos, "final_device")
+    masses = [int(m.mass) for m in dp_table.masses]
+    if masses != [int(x) for x in outcome.row_mass]:
+        raise ValueError("final_device: the outcome is not on this table's rows")
+    S, nf = len(outcome), int(outcome.frag_off[-1])
+    caps = lp_caps(dp_table, outcome) if caps is None else caps
+    row_mod = np.ascontiguousarray(caps[0], dtype=np.uint8)
+    mod_cap = np.ascontiguousarray(caps[1], dtype=np.int32)
+    if len(row_mod) != len(masses) or len(mod_cap) != S:
+        raise ValueError("final_device: caps do not match the table's rows / the outcome's spectra")
+    row_cap = lp_row_caps(dp_table, outcome) if row_cap is None else row_cap
+    row_cap = np.ascontiguousarray(row_cap, dtype=np.int32).reshape(-1)
+    if len(row_cap) != (ALIGN_MAX_LEN + 1) * len(masses):
+        raise ValueError("final_device: row_cap is not a table of 254 lengths by the table's rows")
+    use = _per_fragment(use, nf, "final_device")
+    undecided = _per_spectrum(undecided, S, "final_device")
+    if not undecided.any():
+        return _one_stream(_final_device)(dp_table, outcome, use, row_mod, mod_cap, row_cap, max_combos)
+    from .pipeline_device import _segments
+
+    run = np.flatnonzero(~undecided)
+    rest = np.flatnonzero(undecided)
+    src, _ = _segments(np.asarray(outcome.frag_off, dtype=np.int64), run)
+    sub = outcome.take(run)
+    part = _one_stream(_final_device)(dp_table, sub, use[src], row_mod, mod_cap[run], row_cap, max_combos)
+    where = np.empty(S, np.int64)
+    where[run] = np.arange(len(run))
+    where[rest] = len(run) + np.arange(len(rest))
+    return FinalOutcome.concat([part, FinalOutcome.blank(outcome.take(rest), FINAL_UNDECIDED)]).take(where)
+
+
+def _final_device(dp_table, o, use, row_mod, mod_cap, row_cap, max_combos):
+    import torch
+
+    dt = dp_table.device_table
+    eng = dt.engine
+    dev = torch.device("cuda", eng.device)
+    S, nf, n_pos = len(o), int(o.frag_off[-1]), int(o.pos_off[-1])
+    if S == 0:
+        return FinalOutcome.blank(o)
+
+    def up(x, dtype, n=1):  # (never an empty allocation: the entry point refuses NULL)
+        x = np.ascontiguousarray(x, dtype=dtype).reshape(-1)
+        return torch.as_tensor(x if len(x) else np.zeros(n, dtype), device=dev)
+
+    def out(n, dtype):
+        return torch.empty(max(n, 1), dtype=dtype, device=dev)
+
+    ins = [up(o.seq_len, np.int32), up(o.pos_off, np.int64), up(o.skeleton.view(np.int64), np.int64, 2),
+           up(o.alpha.view(np.int64), np.int64, 2), up(o.frag_off, np.int64), up(o.frag_code, np.uint8),
+           up(o.frag_su, np.float64), up(o.frag_min_end, np.int32), up(o.frag_max_end, np.int32), up(use, np.uint8)]
+    more = [up(row_mod, np.uint8), up(mod_cap, np.int32), up(row_cap, np.int32)]
+    outs = [out(S, torch.uint8), out(S, torch.int64), out(S, torch.int64), out(S, torch.int64), out(S, torch.int32),
+            out(S, torch.int64), out(n_pos, torch.uint8), out(nf, torch.int16), out(nf, torch.int32)]
+    a = _native.FinalArgs()
+    a.n_spec = S
+    (a.seq_len, a.pos_off, a.skeleton, a.alpha, a.frag_off, a.frag_code, a.frag_su, a.frag_min_end, a.frag_max_end,
+     a.frag_use) = (x.data_ptr() for x in ins)
+    a.prec = float(dp_table.precision)
+    a.row_mod, a.mod_cap, a.row_cap = (x.data_ptr() for x in more)
+    a.max_combos = int(max_combos)
+    a.status, a.combos, a.n_feas, a.best, a.n_opt, a.gap, a.seq, a.iv, a.sum = (x.data_ptr() for x in outs)
+    torch.cuda.synchronize(dev)
+    eng.check(eng._lib.sst_final_program_device(dt.handle, ctypes.byref(a)), "sst_final_program_device")
+    eng.synchronize()
+    status, combos, n_feas, best, n_opt, gap, seq, iv, sm = (x.cpu().numpy() for x in outs)
+    return FinalOutcome(frag_off=np.array(o.frag_off, dtype=np.int64), pos_off=np.array(o.pos_off, dtype=np.int64),
+                        status=status[:S], combos=combos[:S].view(np.uint64), n_feas=n_feas[:S].view(np.uint64),
+                        best=best[:S].view(np.uint64), n_opt=n_opt[:S].view(np.uint32), gap=gap[:S].view(np.uint64),
+                        seq=seq[:n_pos], iv=iv[:nf].view(np.uint16), sum=sm[:nf].view(np.uint32))

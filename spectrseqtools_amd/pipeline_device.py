@@ -1730,7 +1730,7 @@ def mirror_outcome(dp_table, obs, su_mass, seq_mass, max_len, breakage_dict, int
 def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=None, intensity=None,
               intensity_cutoff=0.5e6, mass_cutoff=50000, limits=DeviceLimits(), fallback="mirror", name_hash=None,
               trim=True, explanation_masses=None, record=None, align=False, align_split=False, align_caps=False,
-              align_keep=False):
+              align_keep=False, align_final=False, final_max_combos=None):
     """These spectra -> what Predictor.predict holds when it reaches its MILP
     stages (prediction.py:63-103), as a BatchOutcome: the six device stages
     (classify_device, fixpoint_device, bins_device, skeleton_device,
@@ -1780,7 +1780,14 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
     align_host(caps=lp_caps(...), keep=lp_row_caps(...)) on the routed ones):
     the AlignOutcome also carries keep, keep_first and spec_free
     (alignment.lp_decisions: DROP / KEEP / SOLVE); it combines with
-    align_split."""
+    align_split.
+    align_final=True implies align_keep and align_split and also runs the final
+    program by exact enumeration (final_program.py) over the KEEP fragments of
+    every spectrum that holds no LP_SOLVE fragment (final_program.final_use);
+    returns (BatchOutcome, AlignOutcome, FinalOutcome).  Spectra the device ran
+    take final_device, mirror-routed ones final_host; final_max_combos (None:
+    final_program.FINAL_DEFAULT_COMBOS) bounds the assignments enumerated per
+    spectrum.  The first two are what align_keep with align_split returns."""
     from .masses import EXPLANATION_MASSES, TOLERANCE
     from .pipeline import max_len_of
 
@@ -1855,6 +1862,8 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
                                frag_max_end=h["max_end"], breakage_names=names, row_names=dev_out.row_names,
                                row_mass=dev_out.row_mass)
     m_idx = np.flatnonzero(reason)
+    align_keep = align_keep or align_final
+    align_split = align_split or align_final
     align_caps = align_caps or align_keep
     align = align or align_split or align_caps
     if align:
@@ -1862,8 +1871,14 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
 
         dev_al = alignment.align_device(dp_table, dev_out, split=align_split, caps=bool(align_caps),
                                         keep=bool(align_keep))
+    if align_final:
+        from . import final_program
+
+        combos = final_program.FINAL_DEFAULT_COMBOS if final_max_combos is None else final_max_combos
+        use, undecided = final_program.final_use(dev_al)
+        dev_fo = final_program.final_device(dp_table, dev_out, use=use, max_combos=combos, undecided=undecided)
     if not len(m_idx):
-        return (dev_out, dev_al) if align else dev_out
+        return (dev_out, dev_al, dev_fo) if align_final else (dev_out, dev_al) if align else dev_out
     mirrored = [mirror_outcome(dp_table, obs[offsets[g]:offsets[g + 1]], su_seq[g], seq_mass[g], max_len[g],
                                breakage_dict, None if inten is None else inten[offsets[g]:offsets[g + 1]],
                                intensity_cutoff, mass_cutoff, em, int(reason[g])) for g in m_idx.tolist()]
@@ -1873,10 +1888,18 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
     where[m_idx] = len(d_idx) + np.arange(len(m_idx))
     if align:
         cap = int(dp_table.device_table.engine._lib.sst_align_capacity())
-        al = alignment.AlignOutcome.concat(
-            [dev_al] + [alignment.align_host(o, dp_table.tolerance, dp_table.precision, cap, split=align_split,
-                                             caps=alignment.lp_caps(dp_table, o) if align_caps else None,
-                                             keep=alignment.lp_row_caps(dp_table, o) if align_keep else None)
-                        for o in mirrored])
+        m_al = [alignment.align_host(o, dp_table.tolerance, dp_table.precision, cap, split=align_split,
+                                     caps=alignment.lp_caps(dp_table, o) if align_caps else None,
+                                     keep=alignment.lp_row_caps(dp_table, o) if align_keep else None)
+                for o in mirrored]
+        al = alignment.AlignOutcome.concat([dev_al] + m_al)
+        if align_final:
+            m_fo = []
+            for o, a in zip(mirrored, m_al):
+                use, undecided = final_program.final_use(a)
+                m_fo.append(final_program.final_host(o, dp_table.precision, alignment.lp_caps(dp_table, o),
+                                                     alignment.lp_row_caps(dp_table, o), use=use, max_combos=combos,
+                                                     undecided=undecided))
+            return both.take(where), al.take(where), final_program.FinalOutcome.concat([dev_fo] + m_fo).take(where)
         return both.take(where), al.take(where)
     return both.take(where)

@@ -50,7 +50,7 @@ GPU-busy share of its wall time.
 
 Usage: python tools/pipeline_bench.py [--spectra 100000] [--seed 7] [--host-driven]
        [--backend nccl|gloo] [--dump-outcomes DIR] [--as-rank R] [--handoff [--handoff-repeats 3]]
-       [--align | --align-split] [--align-caps | --align-keep] [--modification-rate 0.5]
+       [--align | --align-split] [--align-caps | --align-keep] [--align-final] [--modification-rate 0.5]
 """
 import argparse
 import json
@@ -351,7 +351,44 @@ def keep_record(dp, out, al, split, kern):
                           for k in (_native.K_ALIGN_KEEP, _native.K_ALIGN_SPLIT_KEEP)}}
 
 
-def align_stage(pd, dp, rows, ln, post, kernels, split=False, caps=False, keep=False):
+def final_stage(dp, out, al, kernels, max_combos):
+    """--align-final: the final program by exact enumeration (final_program.
+    final_device) over the certificate's KEEP fragments, spectra that hold an
+    LP_SOLVE fragment left out (final_program.final_use).  Its seconds run from
+    the host arrays in to the host arrays out (uploads, k_final_program,
+    downloads); it records the share of each status over all spectra and over
+    the spectra that have fragments, the TAKE share (final_decisions), and the
+    percentiles of log2(combos) of the SOLVED and of the TOO_LARGE spectra."""
+    from spectrseqtools_amd import final_program as fp
+
+    use, undecided = fp.final_use(al)
+    kernels()
+    t0 = time.perf_counter()
+    fo = fp.final_device(dp, out, use=use, max_combos=max_combos, undecided=undecided)
+    s = time.perf_counter() - t0
+    kern = kernels()
+    live = np.diff(out.frag_off) > 0
+    dec = fp.final_decisions(fo)
+    pct = lambda x: {str(p): float(np.percentile(x, p)) for p in (50, 90, 99, 100)} if len(x) else {}  # noqa: E731
+    log2 = lambda st: pct(np.log2(np.maximum(fo.combos[fo.status == st].astype(np.float64), 1.0)))  # noqa: E731
+    n_live = max(1, int(live.sum()))
+    solved = fo.status == fp.FINAL_SOLVED
+    return {"s": s, "spectra": int(len(fo)), "spectra_with_fragments": int(live.sum()), "max_combos": int(max_combos),
+            "used_fragments_share": float(use.mean()) if len(use) else 0.0,
+            "status_shares": fo.shares(),
+            "status_shares_with_fragments": {name: float(np.count_nonzero((fo.status == st) & live)) / n_live
+                                             for st, name in fp.STATUS_NAMES.items()},
+            "take_share": float(dec.mean()) if len(dec) else 0.0,
+            "take_share_with_fragments": float(dec[live].sum()) / n_live,
+            "take_share_of_solved": float(dec[solved].mean()) if solved.any() else 0.0,
+            "solved_with_several_optima_share": float((fo.n_opt[solved] > 1).mean()) if solved.any() else 0.0,
+            "log2_combos_solved": log2(fp.FINAL_SOLVED), "log2_combos_too_large": log2(fp.FINAL_TOO_LARGE),
+            "assignments_enumerated": int(fo.combos[solved].sum()),
+            "path": "device (sst_final_program_device), host arrays in and out", "kernels": kern,
+            "kernel_ms": {"k_final_program": kern.get("k_final_program", (0.0, 0))[0]}}
+
+
+def align_stage(pd, dp, rows, ln, post, kernels, split=False, caps=False, keep=False, hold=None):
     """--align: the alignment certificate (alignment.align_device) over the
     hand-off of the spectra the stages ran -- wall seconds from the host
     arrays in to the host arrays out (uploads, k_align_windows, downloads), the
@@ -370,7 +407,8 @@ def align_stage(pd, dp, rows, ln, post, kernels, split=False, caps=False, keep=F
     INFEASIBLE and the mod_cap distribution ("caps").
     --align-keep (keep=True, implies caps): the timed call runs in keep mode
     (align_device(caps=True, keep=True): k_align_windows_keep and, with
-    --align-split, k_align_split_keep); "keep" holds keep_record's shares."""
+    --align-split, k_align_split_keep); "keep" holds keep_record's shares.
+    hold: a dict that receives the outcome and its certificate (--align-final)."""
     from spectrseqtools_amd import _native, alignment
 
     S = len(ln.seq_len)
@@ -388,6 +426,8 @@ def align_stage(pd, dp, rows, ln, post, kernels, split=False, caps=False, keep=F
     al = alignment.align_device(dp, out, split=split, caps=caps, keep=keep)
     s = time.perf_counter() - t0
     kern = kernels()
+    if hold is not None:
+        hold.update(outcome=out, certificate=al)
     n = np.diff(out.frag_off)
     internal = (out.frag_code >> 2) & 3 == 0
     rec = {"s": s, "spectra": int(act.sum()), "fragments": int(out.frag_off[-1]), "positions": int(out.pos_off[-1]),
@@ -518,12 +558,20 @@ def main():
                     help="--align-caps in keep mode (align_device(caps=True, keep=True)); alone or with --align-split.  "
                          "The stage also reports the shares of DROP, KEEP and SOLVE, the share of row-free spectra, "
                          "and the FIT fragments left without keep by cause (\"keep\")")
+    ap.add_argument("--align-final", action="store_true",
+                    help="--align-keep --align-split, then the final program by exact enumeration (final_program."
+                         "final_device) over the KEEP fragments: a stage \"final\" with its seconds, k_final_program's "
+                         "time, the status and TAKE shares and the percentiles of log2(combos)")
+    ap.add_argument("--final-max-combos", type=int, default=1 << 20,
+                    help="--align-final: assignments enumerated per spectrum at most (up to 2^22)")
     ap.add_argument("--modification-rate", type=float, default=0.5,
                     help="the sequences' universal modification rate: the synthetic spectra's and the table's "
                          "SequenceInformation's (0.05: the low-modification-rate variant)")
     ap.add_argument("--as-rank", type=int, default=None,
                     help="single process: generate the spectra rank R of a multi-rank run would get")
     args = ap.parse_args()
+    args.align_keep = args.align_keep or args.align_final
+    args.align_split = args.align_split or args.align_final
     args.align_caps = args.align_caps or args.align_keep
     args.align = args.align or args.align_split or args.align_caps
 
@@ -619,7 +667,11 @@ def main():
         lw = pd.length_device(dp, kw, bw.alpha_dev, su_seq[:S0], batch.seq_mass[:S0], trim=False)
         pw = pd.post_skeleton_device(dp, rw, kw, lw)
         if args.align:
-            align_stage(pd, dp, rw, lw, pw, lambda: {}, split=args.align_split, caps=args.align_caps, keep=args.align_keep)
+            held = {}
+            align_stage(pd, dp, rw, lw, pw, lambda: {}, split=args.align_split, caps=args.align_caps, keep=args.align_keep,
+                        hold=held)
+            if args.align_final:
+                final_stage(dp, held["outcome"], held["certificate"], lambda: {}, args.final_max_combos)
         # the reach buffer at length_device's batch budget, as a serving
         # process holds it: the timed stage allocates nothing (its hipMalloc /
         # hipFree of tens of GB took 0.1-3 s from run to run)
@@ -787,11 +839,18 @@ def main():
                                     + (f" ({'RCCL' if args.backend == 'nccl' else 'gloo'})" if dist else " (local)")}
     if rows is not None and args.align:
         barrier()
+        held = {}
         stages["align"] = align_stage(pd, dp, rows, ln, post, kernels, split=args.align_split, caps=args.align_caps,
-                                      keep=args.align_keep)
+                                      keep=args.align_keep, hold=held)
         stages["align"]["s"] = tmax(stages["align"]["s"])
         busy(stages["align"])
         progress("align")
+        if args.align_final:
+            barrier()
+            stages["final"] = final_stage(dp, held["outcome"], held["certificate"], kernels, args.final_max_combos)
+            stages["final"]["s"] = tmax(stages["final"]["s"])
+            busy(stages["final"])
+            progress("final")
     handoff = None
     if rows is not None and args.handoff:
         engine.profile(False)  # (the hand-off is timed by the wall clock alone, outside the stages)
