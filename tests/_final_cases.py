@@ -256,3 +256,126 @@ def random_frags(rng, row_mass, sets, n, precision, noise=3):
         frags.append((AC.code_of(cls in (1, 3), cls in (2, 3)), (true + float(rng.choice([0.0, 0.25, -0.4]))) * precision,
                       100.0, mn, mx))
     return frags
+
+
+# ---------------------------------------------------------------------------
+# the limits of the model and of the kernel (tests/test_gpu_final_limits.py at full size,
+# tests/test_final_model.py and tests/test_align_keep_model.py at a size the brute force enumerates)
+# ---------------------------------------------------------------------------
+def zero_length_specs(rm, precision):
+    """L == 0 (no position, n_pos == 0) with fragments, and what each must be:
+    a START_END fragment and internal ones of positive, zero and negative su
+    (SOLVED: one assignment, the empty interval everywhere, the objective the
+    sum of |qfix|), the same under an alphabet with rows, a used START fragment
+    (SKIPPED: no end lies in [0, -1]) and the same fragment unused.
+    Returns (specs, statuses, the objective of the SOLVED ones without the START fragment)."""
+    frags = [(START_END, 2.5 * precision, 100.0, 0, 0), (INTERNAL, 3.25 * precision, 100.0, 0, 0),
+             (INTERNAL, 0.0, 100.0, 0, 0), (INTERNAL, -1.75 * precision, 100.0, 0, 0)]
+    start = (START, 1.0 * precision, 100.0, 0, 0)
+    bare = loose_spec(rm, [], frags)
+    specs = [bare, dict(bare, alpha=AC.mask([0, 1, 2])), loose_spec(rm, [], frags + [start]),
+             loose_spec(rm, [], frags + [start], use=[1] * 4 + [0])]
+    return specs, [SOLVED, SOLVED, SKIPPED, SOLVED], sum(abs(qfix(f[1], precision)) for f in frags)
+
+
+SU_OUTSIDE = (math.nan, math.inf, -math.inf, -2.0 ** 32, 2.0 ** 32)  # in units of the precision: the model does not hold
+SU_INSIDE = (2.0 ** 32 - 1, -(2.0 ** 32 - 1), -5.3, -0.25)           # ... and holds
+
+
+def su_value_specs(rm, precision, sets=((1, 2), (3,), (2, 4)), values=SU_OUTSIDE + SU_INSIDE):
+    """Per su outside the model and per class a spectrum with that fragment
+    used (SKIPPED) and one with it unused (SOLVED); per su at the model's edge
+    or negative and per class one with it used (SOLVED).  `values`: su in units
+    of the precision.  Returns (specs, statuses)."""
+    sets = [list(rows) for rows in sets]
+    L = len(sets)
+    y = [rows[-1] for rows in sets]
+    pins = prefix_pins(rm, sets, y, range(L), precision)
+    classes = ((INTERNAL, 0, 0), (START, L - 1, 0), (END, 0, L - 1), (START_END, 0, 0))
+    specs, want = [], []
+    for u in values:
+        for code, mn, mx in classes:
+            frags = pins[:1] + [(code, u * precision, 100.0, mn, mx)] + pins[1:]
+            specs.append(loose_spec(rm, sets, frags))
+            want.append(SOLVED if u in SU_INSIDE else SKIPPED)
+            if u not in SU_INSIDE:
+                specs.append(loose_spec(rm, sets, frags, use=[1, 0] + [1] * (L - 1)))
+                want.append(SOLVED)
+    return specs, want
+
+
+def chunk_mask_spec(rm, sets, n_frags, precision, rng, unused=(512, 1024), noise=400):
+    """n_frags noisy fragments of every class over `sets` with the fragments
+    [unused[0], unused[1]) out of use: at 512 records a chunk, the middle one of three."""
+    use = [int(not unused[0] <= j < unused[1]) for j in range(n_frags)]
+    return loose_spec(rm, sets, random_frags(rng, rm, sets, n_frags, precision, noise=noise), use=use)
+
+
+def n_used_specs(rm, precision, n=16390, limit=16384):
+    """n identical START_END fragments over one position of two rows (a, b),
+    the mass row b's, with `limit` of them in use (SOLVED) and with limit + 1
+    (SKIPPED); the unused ones lie at the start, in the middle and at the end.
+    Returns (specs, a, b)."""
+    (a, b), = distinct_pairs(rm, 1)
+    frags = [(START_END, rm[b] * precision, 100.0, 0, 0)] * n
+    specs = []
+    for used in (limit, limit + 1):
+        off = n - used
+        out = set(range(off // 3)) | set(range(n // 2, n // 2 + off // 3))
+        out |= set(range(n - (off - len(out)), n))
+        assert len(out) == off
+        specs.append(loose_spec(rm, [[a, b]], frags, use=[int(j not in out) for j in range(n)]))
+    return specs, a, b
+
+
+def synthetic_masses(n_rows):
+    """n_rows distinct row masses (row 0: 0), no two differences alike nearby."""
+    return [0] + [100003 + 1009 * r + (r * r) % 13 for r in range(1, n_rows)]
+
+
+def row_edge_case(n_rows, precision, rng):
+    """(rm, specs, row_cap) on a synthetic table of n_rows >= 64 rows: free
+    positions over rows {63, 64} and over the last two rows, rows 62 and 64 ..
+    modified, every alphabet and every constrained position carrying all bits at
+    and above n_rows (rows that do not exist, up to the top of the second word)
+    and the alphabet bit 0.  At n_rows == 64 row 64 is such a bit itself.
+    One spectrum's position holds stray bits only (an empty A_i), one is not
+    row-free through its last row, one is row-free only because that row is
+    modified and the cap is 0 (n_rows > 64)."""
+    rm = synthetic_masses(n_rows)
+    top, sec = n_rows - 1, n_rows - 2
+    row_mod = np.zeros(n_rows, np.uint8)
+    row_mod[62] = 1
+    row_mod[64:] = 1
+    stray = ((1 << 128) - 1) & ~((1 << n_rows) - 1)
+    s0, s1 = stray & ((1 << 64) - 1), stray >> 64
+    assert s1 >> 63 and (n_rows > 64 or s1 & 1)
+
+    def build(pos, alpha_rows, n_frags, mod_cap):
+        s = {"L": len(pos), "alpha": AC.mask(alpha_rows), "row_mod": row_mod, "mod_cap": mod_cap, "frags": [],
+             "pos": [AC.mask(rows) if rows else (0, 0) for rows in pos]}
+        sets = CC.position_rows(s, n_rows)  # (before the stray bits: rows below n_rows only)
+        if all(sets):
+            y = [rows[0] for rows in sets]  # (observed mass 350: W = 4 and W_in = 2 at tolerance 1e-5, precision 0.001)
+            s["frags"] = random_frags(rng, rm, sets, n_frags, precision) + \
+                prefix_pins(rm, sets, y, range(len(sets)), precision, obs=350.0)
+        else:
+            s["frags"] = [(START_END, rm[1] * precision, 100.0, 0, 0)] * n_frags
+        s["alpha"] = (s["alpha"][0] | s0 | 1, s["alpha"][1] | s1)
+        s["pos"] = [(p0 | s0, p1 | s1) if p0 | p1 else (0, 0) for p0, p1 in s["pos"]]
+        assert CC.position_rows(s, n_rows) == sets
+        return s
+
+    every = range(n_rows)
+    four = [[63, 64], [top, sec], [1], [62, 63]]
+    five = four + [[2]]
+    specs = [build(four, every, 10, cap) for cap in (4, 1, 0)]
+    specs += [build([[]] * 3, [0, 63, 64, top], 6, 3), build([[]] * 2 + [[64, 63]], [62, 63, 64, sec, top], 6, 1)]
+    empty = build(four, every, 3, 4)
+    empty["pos"][2] = (0, 1 << 63)  # bit 127 alone: constrained, and no row
+    empty["frags"] = empty["frags"][:3]
+    specs.append(empty)
+    specs += [build(five, every, 8, 5), build(five, every, 8, 0)]
+    row_cap = KC.loose_row_cap(n_rows).reshape(KC.MAX_LEN + 1, n_rows)
+    row_cap[5, top] = 0
+    return rm, specs, row_cap.reshape(-1)

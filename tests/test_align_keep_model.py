@@ -232,6 +232,34 @@ def test_row_cap_edges():
     assert loose.spec_free.tolist() == [1] * 4 and loose.keep.all()
 
 
+@pytest.mark.parametrize("split", [False, True])
+@pytest.mark.parametrize("capacity", [1024, 2])
+def test_limit_kinds_against_brute_force(capacity, split):
+    """The kinds of input the GPU tests of a workgroup's later spectra and of
+    the row-count edges hold the kernels to this model on, here the model
+    against the brute force: L == 0 (the empty interval alone; START_END is
+    admissible for it, a terminal fragment is SKIPPED); su that is negative or
+    at the edge of the final program's fixed-point range, in every class; and a
+    65-row table with free positions over rows 63 | 64, modified rows from 64
+    on and every alphabet and constrained position with all bits from 65 to
+    127 set."""
+    import _final_cases as FC
+
+    zero, _, _ = FC.zero_length_specs(BIG, PREC)
+    values, _ = FC.su_value_specs(BIG, PREC, values=FC.SU_INSIDE)
+    specs = zero + values
+    row_cap = KC.loose_row_cap(len(BIG))
+    got = host(specs, BIG, row_cap, capacity, split)
+    KC.assert_equal7(got, KC.brute_keep(specs, BIG, row_cap, TOL, PREC, capacity, split), ("zero, su", capacity, split))
+    first = got.first[:4].tolist()
+    assert first[2] == 0xFFFF and got.status[:4].tolist() == [AC.FIT, AC.FIT, AC.FIT, AC.FIT]  # (W = 4 around 0)
+    assert got.status[12] == AC.SKIPPED and got.spec_free[:4].tolist() == [1, 1, 1, 1]
+    rm, specs, row_cap = FC.row_edge_case(65, PREC, np.random.default_rng(8))
+    got = host(specs, rm, row_cap, capacity, split)
+    KC.assert_equal7(got, KC.brute_keep(specs, rm, row_cap, TOL, PREC, capacity, split), ("65 rows", capacity, split))
+    assert got.spec_free.tolist() == [1, 1, 1, 1, 1, 0, 0, 1] and got.keep.sum() >= 10
+
+
 def test_lp_row_caps():
     """row_cap[L * n_rows + r] = int(np.ceil(rate * L)) with the rate of the row
     that holds row r's FIRST name; a name in two rows is a ValueError."""

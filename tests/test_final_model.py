@@ -212,6 +212,41 @@ def test_final_use_and_outcome_plumbing():
         FP.final_host(o, PREC, caps, row_cap, use=np.ones(3))
 
 
+def test_limit_kinds_against_brute_force():
+    """The kinds of input tests/test_gpu_final_limits.py holds the kernel to the
+    host model on, here the host model against the brute force at a size it
+    enumerates: L == 0; su that is not finite, at the fixed-point range's edge
+    and negative, used and unused, in every class; 1100 fragments with the
+    middle 512 out of use, over 8 assignments; 16384 and 16385 used fragments
+    over 2 assignments."""
+    rm = [0, 30011, 41017, 52021, 63029, 74051, 85061]
+    rng = np.random.default_rng(6)
+    zero, zero_want, objective = FC.zero_length_specs(rm, PREC)
+    values, su_want = FC.su_value_specs(rm, PREC)
+    masked = FC.chunk_mask_spec(rm, [[1, 2], [3, 4], [5, 6]], 1100, PREC, rng)
+    edge, a, b = FC.n_used_specs(rm, PREC)
+    specs = zero + values + [masked, dict(masked, use=None)] + edge
+    got = FC.host(specs, rm, KC.loose_row_cap(len(rm)), PREC)
+    FC.assert_equal9(got, FC.brute_final(specs, rm, KC.loose_row_cap(len(rm)), PREC, 1 << 20), "limit kinds")
+    assert got.status.tolist() == zero_want + su_want + [FC.SOLVED] * 3 + [FC.SKIPPED]
+    assert got.best[:2].tolist() == [objective] * 2 and (got.iv[:8] == 0xFFFF).all() and got.combos[:4].tolist() == [1, 1, 0, 1]
+    at = len(zero) + len(values)
+    assert got.combos[at] == 8 and got.best[at] < got.best[at + 1] and got.n_used()[at:].tolist() == [588, 1100, 16384, 0]
+    assert got.gap[at + 2] == 16384 * FC.FIX * abs(rm[b] - rm[a]) and got.combos[at + 2] == 2
+
+
+def test_bits_above_the_row_count_against_brute_force():
+    """A 65-row table, free positions over rows 63 | 64 (the two words of a
+    mask), modified rows from 64 on, every alphabet and constrained position
+    with all bits from 65 to 127 set, and bit 0 of the alphabet: the rows that
+    do not exist are in no A_i."""
+    rm, specs, row_cap = FC.row_edge_case(65, PREC, np.random.default_rng(7))
+    got = FC.host(specs, rm, row_cap, PREC)
+    FC.assert_equal9(got, FC.brute_final(specs, rm, row_cap, PREC, 1 << 20), "65 rows")
+    assert got.combos.tolist() == [8, 8, 8, 8, 18, 0, 8, 8] and got.status[4:7].tolist() == [FC.SOLVED, FC.INFEASIBLE, FC.NOT_FREE]
+    assert all(s["alpha"][1] >> 63 and s["alpha"][0] & 1 for s in specs) and got.n_feas[1] < got.combos[1]
+
+
 def test_model_limits():
     """|u| >= 2^32, a u that is not finite and an out-of-range end make the
     spectrum SKIPPED only where the fragment is used; combos saturates."""
