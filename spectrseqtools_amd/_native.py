@@ -981,9 +981,7 @@ class DeviceTable:
                           "sst_is_valid_batch_device")
 
     def explain(self, masses, thresholds, tolerance, precision, max_mods, with_memo=True, cap=2 ** 32):
-        m = np.ascontiguousarray(masses, dtype=np.float64)
-        t = None if thresholds is None else np.ascontiguousarray(thresholds, dtype=np.float64)
-        mods_arr, scalar = _mods(max_mods, len(m))
+        m, t, mods_arr, scalar = _host_batch(masses, thresholds, max_mods)
         h = ctypes.c_void_p()
         self.engine.check(self.engine._lib.sst_explain_batch(self.handle, _ptr(m), _ptr(t), len(m), float(tolerance),
                                                              float(precision), _ptr(mods_arr), scalar,
@@ -993,9 +991,7 @@ class DeviceTable:
 
     def explain_recursion(self, masses, thresholds, tolerance, precision, max_mods, cap=2 ** 32):
         """explain_mass_with_recursion, batched; max_mods: np.inf / non-negative integers (scalar or per mass)."""
-        m = np.ascontiguousarray(masses, dtype=np.float64)
-        t = None if thresholds is None else np.ascontiguousarray(thresholds, dtype=np.float64)
-        mods_arr, scalar = _mods(max_mods, len(m))
+        m, t, mods_arr, scalar = _host_batch(masses, thresholds, max_mods)
         h = ctypes.c_void_p()
         self.engine.check(self.engine._lib.sst_explain_recursion_batch(self.handle, _ptr(m), _ptr(t), len(m),
                                                                        float(tolerance), float(precision),
@@ -1004,34 +1000,35 @@ class DeviceTable:
                           "sst_explain_recursion_batch")
         return ExplainResult(self.engine, h, len(m)).fetch()
 
+    def _queue(self, export, args, n, reuse=None, set_n=True):
+        """Queue the device explain call `export(table, *args, &result)` (no
+        host sync) into `reuse`, an ExplainResult of this engine whose buffers
+        are reused, or into a new result of n queries.  set_n: the call runs n
+        queries (else n is a capacity and the pass produces its own queries)."""
+        h = ctypes.c_void_p(reuse.handle.value if reuse is not None else None)
+        self.engine.check(getattr(self.engine._lib, export)(self.handle, *args, ctypes.byref(h)), export)
+        if reuse is None:
+            return ExplainResult(self.engine, h, n)
+        if set_n:
+            reuse.n = n
+        return reuse
+
     def explain_device(self, d_mass, d_thr, n, tolerance, precision, max_mods_scalar, d_mods=None, with_memo=True,
                        cap=2 ** 32, reuse=None):
         """Queue an explain batch on device buffers (no host sync).  `reuse`: an
         ExplainResult of this engine with capacity >= n whose buffers are reused."""
-        h = ctypes.c_void_p(reuse.handle.value if reuse is not None else None)
-        self.engine.check(self.engine._lib.sst_explain_batch_device(self.handle, d_mass, d_thr, int(n),
-                                                                    float(tolerance), float(precision), d_mods,
-                                                                    int(max_mods_scalar), int(bool(with_memo)),
-                                                                    int(cap), ctypes.byref(h)),
-                          "sst_explain_batch_device")
-        if reuse is not None:
-            reuse.n = n
-            return reuse
-        return ExplainResult(self.engine, h, n)
+        return self._queue("sst_explain_batch_device",
+                           (d_mass, d_thr, int(n), float(tolerance), float(precision), d_mods, int(max_mods_scalar),
+                            int(bool(with_memo)), int(cap)), n, reuse)
 
     def explain_alpha_device(self, d_mass, d_thr, d_spec, d_alpha, n, tolerance, precision, max_mods_scalar,
                              d_mods=None, with_memo=True, cap=2 ** 32, reuse=None):
         """sst_explain_alpha_batch_device: explain_device with query i answered
         on the reduced alphabet d_alpha[d_spec[i]] (u64 row-mask pairs over this
         table's rows), as the rebuilt reduced table would answer it."""
-        h = ctypes.c_void_p(reuse.handle.value if reuse is not None else None)
-        self.engine.check(self.engine._lib.sst_explain_alpha_batch_device(
-            self.handle, d_mass, d_thr, d_spec, d_alpha, int(n), float(tolerance), float(precision), d_mods,
-            int(max_mods_scalar), int(bool(with_memo)), int(cap), ctypes.byref(h)), "sst_explain_alpha_batch_device")
-        if reuse is not None:
-            reuse.n = n
-            return reuse
-        return ExplainResult(self.engine, h, n)
+        return self._queue("sst_explain_alpha_batch_device",
+                           (d_mass, d_thr, d_spec, d_alpha, int(n), float(tolerance), float(precision), d_mods,
+                            int(max_mods_scalar), int(bool(with_memo)), int(cap)), n, reuse)
 
     def explain_alpha_lens_device(self, d_mass, d_thr, d_spec, d_alpha, d_qlen, caps_by_len, n, tolerance,
                                   precision, d_mods, cap=2 ** 32):
@@ -1039,53 +1036,45 @@ class DeviceTable:
         per-query budgets -- query i's row caps caps_by_len[d_qlen[i]] (host
         [n_lens, n_rows] ints), its max_modifications d_mods[i]."""
         caps = np.ascontiguousarray(caps_by_len, dtype=np.int64)
-        h = ctypes.c_void_p(None)
-        self.engine.check(self.engine._lib.sst_explain_alpha_lens_batch_device(
-            self.handle, d_mass, d_thr, d_spec, d_alpha, d_qlen, caps.ctypes.data, int(caps.shape[0]), int(n),
-            float(tolerance), float(precision), d_mods, int(cap), ctypes.byref(h)),
-            "sst_explain_alpha_lens_batch_device")
-        return ExplainResult(self.engine, h, n)
+        return self._queue("sst_explain_alpha_lens_batch_device",
+                           (d_mass, d_thr, d_spec, d_alpha, d_qlen, caps.ctypes.data, int(caps.shape[0]), int(n),
+                            float(tolerance), float(precision), d_mods, int(cap)), n)
+
+    def _upload_alpha(self, masses, thresholds, spec, alpha, max_mods, qlen=None):
+        """A host alpha batch as device tensors, uploaded: masses, thresholds,
+        spec, alpha and the per-query max_mods (then qlen, when given)."""
+        import torch
+
+        dev = torch.device("cuda", self.engine.device)
+        mods = np.broadcast_to(np.asarray(max_mods, dtype=np.int64), (len(masses),))
+        host = [np.ascontiguousarray(masses, dtype=np.float64), np.ascontiguousarray(thresholds, dtype=np.float64),
+                np.ascontiguousarray(spec, dtype=np.int32), np.ascontiguousarray(alpha, dtype=np.uint64).view(np.int64),
+                np.ascontiguousarray(mods)]
+        if qlen is not None:
+            host.append(np.ascontiguousarray(qlen, dtype=np.int32))
+        tensors = [torch.as_tensor(a, device=dev) for a in host]
+        torch.cuda.synchronize(dev)
+        return tensors
 
     def explain_alpha(self, masses, thresholds, spec, alpha, tolerance, precision, max_mods, with_memo=True,
                       cap=2 ** 32):
         """Host-buffer form of explain_alpha_device (tests, small batches):
         uploads the inputs, settles and fetches the result."""
-        import torch
-
-        dev = torch.device("cuda", self.engine.device)
-        n = len(masses)
-        dm = torch.as_tensor(np.ascontiguousarray(masses, dtype=np.float64), device=dev)
-        dt = torch.as_tensor(np.ascontiguousarray(thresholds, dtype=np.float64), device=dev)
-        ds = torch.as_tensor(np.ascontiguousarray(spec, dtype=np.int32), device=dev)
-        da = torch.as_tensor(np.ascontiguousarray(alpha, dtype=np.uint64).view(np.int64), device=dev)
-        mods = np.broadcast_to(np.asarray(max_mods, dtype=np.int64), (n,))
-        dmods = torch.as_tensor(np.ascontiguousarray(mods), device=dev)
-        torch.cuda.synchronize(dev)
-        res = self.explain_alpha_device(dm.data_ptr(), dt.data_ptr(), ds.data_ptr(), da.data_ptr(), n, tolerance,
-                                        precision, 0, d_mods=dmods.data_ptr(), with_memo=with_memo, cap=cap)
+        dm, dt, ds, da, dmods = self._upload_alpha(masses, thresholds, spec, alpha, max_mods)
+        res = self.explain_alpha_device(dm.data_ptr(), dt.data_ptr(), ds.data_ptr(), da.data_ptr(), len(masses),
+                                        tolerance, precision, 0, d_mods=dmods.data_ptr(), with_memo=with_memo,
+                                        cap=cap)
         res.fetch_device()
-        del dm, dt, ds, da, dmods
         return res
 
     def explain_alpha_lens(self, masses, thresholds, spec, alpha, qlen, caps_by_len, max_mods, tolerance, precision):
         """Host-buffer form of explain_alpha_lens_device (tests): query i with
         row caps caps_by_len[qlen[i]] and max_mods[i]; settles and fetches."""
-        import torch
-
-        dev = torch.device("cuda", self.engine.device)
-        n = len(masses)
-        dm = torch.as_tensor(np.ascontiguousarray(masses, dtype=np.float64), device=dev)
-        dt = torch.as_tensor(np.ascontiguousarray(thresholds, dtype=np.float64), device=dev)
-        ds = torch.as_tensor(np.ascontiguousarray(spec, dtype=np.int32), device=dev)
-        da = torch.as_tensor(np.ascontiguousarray(alpha, dtype=np.uint64).view(np.int64), device=dev)
-        dq = torch.as_tensor(np.ascontiguousarray(qlen, dtype=np.int32), device=dev)
-        dmods = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(np.asarray(max_mods, np.int64), (n,))),
-                                device=dev)
-        torch.cuda.synchronize(dev)
+        dm, dt, ds, da, dmods, dq = self._upload_alpha(masses, thresholds, spec, alpha, max_mods, qlen)
         res = self.explain_alpha_lens_device(dm.data_ptr(), dt.data_ptr(), ds.data_ptr(), da.data_ptr(),
-                                             dq.data_ptr(), caps_by_len, n, tolerance, precision, dmods.data_ptr())
+                                             dq.data_ptr(), caps_by_len, len(masses), tolerance, precision,
+                                             dmods.data_ptr())
         res.fetch_device()
-        del dm, dt, ds, da, dq, dmods
         return res
 
     def step_rows_device(self, d_obs, d_peak_off, n_spec, n_peaks, d_su_seq, shifts, sides, d_valid_out, max_weight,
@@ -1096,15 +1085,11 @@ class DeviceTable:
         peaks, all on the device (queued, no host sync)."""
         sh = np.ascontiguousarray(shifts, dtype=np.float64)
         sd = np.ascontiguousarray(sides, dtype=np.uint8)
-        h = ctypes.c_void_p(reuse.handle.value if reuse is not None else None)
-        self.engine.check(self.engine._lib.sst_step_rows_device(
-            self.handle, d_obs, d_peak_off, int(n_spec), int(n_peaks), d_intensity, float(intensity_cutoff),
-            float(mass_cutoff), d_su_seq, _ptr(sh), _ptr(sd), len(sh), float(max_weight), float(tolerance),
-            float(precision), int(max_mods_scalar), int(cap), int(max_queries), d_valid_out, ctypes.byref(h)),
-            "sst_step_rows_device")
-        if reuse is not None:
-            return reuse
-        return ExplainResult(self.engine, h, int(max_queries))
+        return self._queue("sst_step_rows_device",
+                           (d_obs, d_peak_off, int(n_spec), int(n_peaks), d_intensity, float(intensity_cutoff),
+                            float(mass_cutoff), d_su_seq, _ptr(sh), _ptr(sd), len(sh), float(max_weight),
+                            float(tolerance), float(precision), int(max_mods_scalar), int(cap), int(max_queries),
+                            d_valid_out), int(max_queries), reuse, set_n=False)
 
     def step_device(self, d_obs, n_peaks, shifts, d_valid_out, d_mass, d_thr, n, tolerance, precision,
                     max_mods_scalar, d_mods=None, with_memo=True, cap=2 ** 32, reuse=None):
@@ -1112,16 +1097,10 @@ class DeviceTable:
         d_valid_out, breakage-major) and an explain batch, queued together (one
         launch when the scan packs its own result).  Returns the ExplainResult."""
         sh = np.ascontiguousarray(shifts, dtype=np.float64)
-        h = ctypes.c_void_p(reuse.handle.value if reuse is not None else None)
-        self.engine.check(self.engine._lib.sst_step_device(self.handle, d_obs, int(n_peaks), _ptr(sh), len(sh),
-                                                           d_valid_out, d_mass, d_thr, int(n), float(tolerance),
-                                                           float(precision), d_mods, int(max_mods_scalar),
-                                                           int(bool(with_memo)), int(cap), ctypes.byref(h)),
-                          "sst_step_device")
-        if reuse is not None:
-            reuse.n = n
-            return reuse
-        return ExplainResult(self.engine, h, n)
+        return self._queue("sst_step_device",
+                           (d_obs, int(n_peaks), _ptr(sh), len(sh), d_valid_out, d_mass, d_thr, int(n),
+                            float(tolerance), float(precision), d_mods, int(max_mods_scalar), int(bool(with_memo)),
+                            int(cap)), n, reuse)
 
     def close(self):
         if self.handle:
@@ -1133,6 +1112,14 @@ class DeviceTable:
             self.close()
         except Exception:
             pass
+
+
+def _host_batch(masses, thresholds, max_mods):
+    """(m, t, mods_arr, scalar) of a host-pointer explain call: contiguous
+    float64 masses and thresholds (or None), max_mods as _mods gives it."""
+    m = np.ascontiguousarray(masses, dtype=np.float64)
+    t = None if thresholds is None else np.ascontiguousarray(thresholds, dtype=np.float64)
+    return (m, t) + _mods(max_mods, len(m))
 
 
 def _mods(max_mods, n):

@@ -149,6 +149,21 @@ struct LenBudgets {
   const uint32_t* never = nullptr;
 };
 
+// what an explain pass is queued with (device pointers); the result keeps its
+// current pass's, for the deferred-class launch and the retries of settle()
+struct PassSpec {
+  sst_table* t;
+  const double *mass, *thr;
+  const int64_t* mods;
+  int64_t mods_scalar;
+  double tol, prec;
+  int with_memo;
+  uint64_t cap;
+  const uint64_t* alpha;  // per-query alphabets (sst_explain_alpha_batch_device) or null
+  const int32_t* spec;
+  LenBudgets lb;          // per-query budgets or none
+};
+
 struct sst_result {
   sst_ctx* ctx = nullptr;
   int64_t n = 0;
@@ -185,18 +200,7 @@ struct sst_result {
   const sst_table* sized_for = nullptr;
   bool sized_bitset = false;
   bool fused_pass = false;    // the pass's scan packed its own queries' result (dense records + payload)
-  struct {
-    sst_table* t;
-    const double *mass, *thr;
-    const int64_t* mods;
-    int64_t mods_scalar;
-    double tol, prec;
-    int with_memo;
-    uint64_t cap;
-    const uint64_t* alpha;  // per-query alphabets (sst_explain_alpha_batch_device) or null
-    const int32_t* spec;
-    LenBudgets lb;          // per-query budgets or none
-  } pass{};
+  PassSpec pass{};
   uint64_t arena_bytes = 0;
   uint64_t n_hits = 0, payload_bytes = 0;
   // the fused scan's part of the result (its header): the first scan_hits
@@ -236,6 +240,36 @@ int fail(sst_ctx* c, int code, const std::string& msg) {
 
 int set_device(sst_ctx* c) {
   HIP_OK(c, hipSetDevice(c->device));
+  return SST_OK;
+}
+
+// Host-pointer calls: the batch copied into the ctx's staging buffers on its
+// stream.  thr and mods are optional: a null device pointer where the host's
+// was.  The buffers hold max(n, 1) elements, so that an empty batch still
+// passes a non-null mass pointer; n_out sizes out_valid (0: not used).
+struct Staged {
+  const double *mass, *thr;
+  const int64_t* mods;
+};
+int stage_inputs(sst_ctx* c, const double* mass, const double* thr, const int64_t* mods, int64_t n, size_t n_out,
+                 Staged* s) {
+  const size_t bytes = (size_t)std::max<int64_t>(n, 1) * 8;
+  if (!c->in_mass.ensure(bytes) || (thr && !c->in_thr.ensure(bytes)) || (mods && !c->in_mods.ensure(bytes)) ||
+      !c->out_valid.ensure(n_out))
+    return fail(c, SST_E_NOMEM, "device allocation failed (staging)");
+  if (n) {
+    HIP_OK(c, hipMemcpyAsync(c->in_mass.p, mass, n * 8, hipMemcpyHostToDevice, c->stream));
+    if (thr) HIP_OK(c, hipMemcpyAsync(c->in_thr.p, thr, n * 8, hipMemcpyHostToDevice, c->stream));
+    if (mods) HIP_OK(c, hipMemcpyAsync(c->in_mods.p, mods, n * 8, hipMemcpyHostToDevice, c->stream));
+  }
+  *s = {(const double*)c->in_mass.p, thr ? (const double*)c->in_thr.p : nullptr,
+        mods ? (const int64_t*)c->in_mods.p : nullptr};
+  return SST_OK;
+}
+// ... and the n answer bytes of out_valid copied back, complete on return
+int unstage_valid(sst_ctx* c, int8_t* out, size_t n) {
+  HIP_OK(c, hipMemcpyAsync(out, c->out_valid.p, n, hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(c, hipStreamSynchronize(c->stream));
   return SST_OK;
 }
 
@@ -830,8 +864,7 @@ int sst_is_valid_batch_device(sst_table* t, const double* d_mass, const double* 
   std::lock_guard<std::recursive_mutex> g(c->mu);
   if (int rc = set_device(c)) return rc;
   Prof p(c, SST_K_IS_VALID);
-  HIP_OK(c, launch_is_valid(t->args.valid, t->args.limit, t->args.full_lo, t->args.full_hi, t->args.first_reach, d_mass,
-                            d_thr, n, tol, prec, d_out, c->stream));
+  HIP_OK(c, launch_is_valid(t->args, d_mass, d_thr, n, tol, prec, d_out, c->stream));
   return SST_OK;
 }
 
@@ -845,8 +878,7 @@ int sst_is_valid_peaks_device(sst_table* t, const double* d_obs, int64_t n_peaks
   std::lock_guard<std::recursive_mutex> g(c->mu);
   if (int rc = set_device(c)) return rc;
   Prof p(c, SST_K_IS_VALID);
-  HIP_OK(c, launch_is_valid_peaks(t->args.valid, t->args.limit, t->args.full_lo, t->args.full_hi, t->args.first_reach,
-                                  d_obs, n_peaks, shifts, n_shifts, tol, prec, d_out, c->stream));
+  HIP_OK(c, launch_is_valid_peaks(t->args, PeaksJob{d_obs, n_peaks, shifts, n_shifts, d_out}, tol, prec, c->stream));
   return SST_OK;
 }
 int sst_is_valid_peaks(sst_table* t, const double* obs, int64_t n_peaks, const double* shifts, int n_shifts,
@@ -859,15 +891,11 @@ int sst_is_valid_peaks(sst_table* t, const double* obs, int64_t n_peaks, const d
   sst_ctx* c = t->ctx;
   std::lock_guard<std::recursive_mutex> g(c->mu);
   if (int rc = set_device(c)) return rc;
-  if (!c->in_mass.ensure(n_peaks * 8) || !c->out_valid.ensure(n))
-    return fail(c, SST_E_NOMEM, "device allocation failed (staging)");
-  HIP_OK(c, hipMemcpyAsync(c->in_mass.p, obs, n_peaks * 8, hipMemcpyHostToDevice, c->stream));
-  if (int rc = sst_is_valid_peaks_device(t, (const double*)c->in_mass.p, n_peaks, shifts, n_shifts, tol, prec,
-                                         (int8_t*)c->out_valid.p))
+  Staged s;
+  if (int rc = stage_inputs(c, obs, nullptr, nullptr, n_peaks, n, &s)) return rc;
+  if (int rc = sst_is_valid_peaks_device(t, s.mass, n_peaks, shifts, n_shifts, tol, prec, (int8_t*)c->out_valid.p))
     return rc;
-  HIP_OK(c, hipMemcpyAsync(out, c->out_valid.p, n, hipMemcpyDeviceToHost, c->stream));
-  HIP_OK(c, hipStreamSynchronize(c->stream));
-  return SST_OK;
+  return unstage_valid(c, out, n);
 }
 int sst_is_valid_batch(sst_table* t, const double* mass, const double* thr, int64_t n, double tol, double prec,
                        int8_t* out) {
@@ -876,16 +904,10 @@ int sst_is_valid_batch(sst_table* t, const double* mass, const double* thr, int6
   sst_ctx* c = t->ctx;
   std::lock_guard<std::recursive_mutex> g(c->mu);
   if (int rc = set_device(c)) return rc;
-  if (!c->in_mass.ensure(n * 8) || (thr && !c->in_thr.ensure(n * 8)) || !c->out_valid.ensure(n))
-    return fail(c, SST_E_NOMEM, "device allocation failed (staging)");
-  HIP_OK(c, hipMemcpyAsync(c->in_mass.p, mass, n * 8, hipMemcpyHostToDevice, c->stream));
-  if (thr) HIP_OK(c, hipMemcpyAsync(c->in_thr.p, thr, n * 8, hipMemcpyHostToDevice, c->stream));
-  if (int rc = sst_is_valid_batch_device(t, (const double*)c->in_mass.p, thr ? (const double*)c->in_thr.p : nullptr, n,
-                                         tol, prec, (int8_t*)c->out_valid.p))
-    return rc;
-  HIP_OK(c, hipMemcpyAsync(out, c->out_valid.p, n, hipMemcpyDeviceToHost, c->stream));
-  HIP_OK(c, hipStreamSynchronize(c->stream));
-  return SST_OK;
+  Staged s;
+  if (int rc = stage_inputs(c, mass, thr, nullptr, n, n, &s)) return rc;
+  if (int rc = sst_is_valid_batch_device(t, s.mass, s.thr, n, tol, prec, (int8_t*)c->out_valid.p)) return rc;
+  return unstage_valid(c, out, n);
 }
 
 }  // extern "C"
@@ -921,6 +943,10 @@ void free_result_bufs(sst_result* r) {
   r->hdr_host = nullptr;
   if (r->settle_ev) (void)hipEventDestroy(r->settle_ev);
   r->settle_ev = nullptr;
+}
+void destroy_result(sst_result* r) {
+  free_result_bufs(r);
+  delete r;
 }
 
 uint64_t* ctl_block(sst_result* r, int parity) { return (uint64_t*)r->ctl.p + parity * kCtlWords; }
@@ -1019,21 +1045,28 @@ void fold_scan_limits(const TableArgs& a, QueryArgs& q) {
   q.cap32 = (uint32_t)std::min<uint64_t>(q.cap_count, UINT32_MAX);
 }
 
+// The kernels' view of a pass over n queries: every kernel of the pass gets
+// its QueryArgs from here, so that they cannot disagree about the query.
+// `ta` is the table view the scan limits are folded from; only the scan
+// bodies read those (the pass's scan passes its own view, see explain_pass).
+QueryArgs query_args(const PassSpec& p, int64_t n, const TableArgs& ta, uint64_t node_budget) {
+  QueryArgs q{p.mass, p.thr, p.mods, p.mods_scalar, n, p.tol, p.prec, 1.0 / p.prec, p.with_memo, p.cap, node_budget};
+  fold_scan_limits(ta, q);
+  q.alpha = p.alpha;
+  q.spec = p.spec;
+  q.comp = (int)p.t->C;
+  q.qlen = p.lb.qlen;
+  q.caps_len = p.lb.caps;
+  q.capz_len = p.lb.capz;
+  q.never_len = p.lb.never;
+  return q;
+}
+
 // the deferred-class launch of a pass (after the pair scan it also runs the
 // SHALLOW windows, one wave per block)
 int launch_tail(sst_table* t, sst_result* r) {
   sst_ctx* c = t->ctx;
-  const auto& ps = r->pass;
-  QueryArgs q{ps.mass, ps.thr, ps.mods, ps.mods_scalar, r->n, ps.tol, ps.prec, 1.0 / ps.prec, ps.with_memo, ps.cap,
-              kNodeBudget};
-  fold_scan_limits(t->args, q);
-  q.alpha = ps.alpha;
-  q.spec = ps.spec;
-  q.comp = (int)t->C;
-  q.qlen = ps.lb.qlen;
-  q.caps_len = ps.lb.caps;
-  q.capz_len = ps.lb.capz;
-  q.never_len = ps.lb.never;
+  const QueryArgs q = query_args(r->pass, r->n, t->args, kNodeBudget);
   OutArgs o = out_args(r);
 #ifdef SST_DIAG  // diagnostic builds only (make DIAG=1): roles switched off, results invalid
   {
@@ -1098,22 +1131,20 @@ int launch_pack(sst_result* r, const uint64_t* scan_hdr = nullptr) {
 // deferred-class launch (eager_tail; otherwise settle() launches it only if
 // the scan routed a window to it) and the result pack.  Tables without the
 // pair list run k_bitset_scan + k_explain_expand and always the tail.
-// is_valid over peaks x breakage weights issued with a pass (sst_step_device)
-struct PeaksJob {
-  const double* obs;
-  int64_t n;
-  const double* shifts;
-  int n_shifts;
-  int8_t* out;
-};
-
-int explain_pass(sst_table* t, sst_result* r, const double* d_mass, const double* d_thr, const int64_t* d_mods,
-                 int64_t mods_scalar, double tol, double prec, int with_memo, uint64_t cap_count, bool eager_tail,
-                 const PeaksJob* peaks = nullptr, const uint64_t* d_alpha = nullptr, const int32_t* d_spec = nullptr,
-                 const LenBudgets* lens = nullptr) {
+// `peaks` (sst_step_device): is_valid over peaks x breakage weights issued
+// with the pass, in the scan's launch when it can be (k_step).
+int launch_peaks_alone(sst_table* t, const PeaksJob& peaks, double tol, double prec) {
   sst_ctx* c = t->ctx;
-  const LenBudgets lb = lens ? *lens : LenBudgets{};
-  r->pass = {t, d_mass, d_thr, d_mods, mods_scalar, tol, prec, with_memo, cap_count, d_alpha, d_spec, lb};
+  Prof p(c, SST_K_IS_VALID);
+  HIP_OK(c, launch_is_valid_peaks(t->args, peaks, tol, prec, c->stream));
+  return SST_OK;
+}
+
+int explain_pass(sst_result* r, const PassSpec& p, bool eager_tail, const PeaksJob* peaks = nullptr) {
+  sst_table* const t = p.t;
+  sst_ctx* c = t->ctx;
+  const bool has_peaks = peaks && peaks->n > 0 && peaks->n_shifts > 0;
+  r->pass = p;
   r->pass_stream = c->stream;
   r->settle_ev_pending = false;
   r->rows_pass = false;
@@ -1131,12 +1162,8 @@ int explain_pass(sst_table* t, sst_result* r, const double* d_mass, const double
   r->tail_ran = false;
   r->arrays_ready = false;
   r->bitset_scan = !t->args.pairs_enabled || (r->sized_for == t && r->sized_bitset);
-  if (n == 0 && peaks && peaks->n > 0 && peaks->n_shifts > 0) {
-    Prof p(c, SST_K_IS_VALID);
-    HIP_OK(c, launch_is_valid_peaks(t->args.valid, t->args.limit, t->args.full_lo, t->args.full_hi,
-                                    t->args.first_reach, peaks->obs, peaks->n, peaks->shifts, peaks->n_shifts, tol,
-                                    prec, peaks->out, c->stream));
-  }
+  if (n == 0 && has_peaks)
+    if (int rc = launch_peaks_alone(t, *peaks, p.tol, p.prec)) return rc;
   if (n == 0) {  // nothing to launch: an empty, settled result
     // no scan ran to zero what the next pass reads: its control block and
     // its half of the look-back aggregates
@@ -1165,17 +1192,9 @@ int explain_pass(sst_table* t, sst_result* r, const double* d_mass, const double
   // SHALLOW role know the full alphabet only) and routes every window with
   // values to the deferred roles, which walk the alphabet's rows only
   TableArgs ta = t->args;
-  if (d_alpha) ta.pair_lim = 0, ta.shallow_hi = 0;
+  if (p.alpha) ta.pair_lim = 0, ta.shallow_hi = 0;
   if (r->bitset_scan) ta.pairs_enabled = 0;  // (a result sized before the table was certified)
-  QueryArgs q{d_mass, d_thr, d_mods, mods_scalar, n, tol, prec, 1.0 / prec, with_memo, cap_count, kNodeBudget};
-  fold_scan_limits(ta, q);
-  q.alpha = d_alpha;
-  q.spec = d_spec;
-  q.comp = (int)t->C;
-  q.qlen = lb.qlen;
-  q.caps_len = lb.caps;
-  q.capz_len = lb.capz;
-  q.never_len = lb.never;
+  const QueryArgs q = query_args(p, n, ta, kNodeBudget);
   OutArgs o = out_args(r);
   // the pair scan packs its own result (and writes the header) when no
   // deferred-class launch follows it in this pass
@@ -1192,24 +1211,19 @@ int explain_pass(sst_table* t, sst_result* r, const double* d_mass, const double
     o.dbg = dbg ? atoi(dbg) : 0;
 #endif
   }
-  const bool step = peaks && peaks->n > 0 && peaks->n_shifts == 4 && fused;
-  if (peaks && peaks->n > 0 && peaks->n_shifts > 0 && !step) {  // A7 in its own launch, before the pass
-    Prof p(c, SST_K_IS_VALID);
-    HIP_OK(c, launch_is_valid_peaks(t->args.valid, t->args.limit, t->args.full_lo, t->args.full_hi,
-                                    t->args.first_reach, peaks->obs, peaks->n, peaks->shifts, peaks->n_shifts, tol,
-                                    prec, peaks->out, c->stream));
-  }
+  const bool step = has_peaks && peaks->n_shifts == 4 && fused;
+  if (has_peaks && !step)  // A7 in its own launch, before the pass
+    if (int rc = launch_peaks_alone(t, *peaks, p.tol, p.prec)) return rc;
   {
-    Prof p(c, SST_K_EXPLAIN_MAIN);
+    Prof prof(c, SST_K_EXPLAIN_MAIN);
     if (step)
-      HIP_OK(c, launch_step(t->args, q, o, r->n_wg, peaks->obs, peaks->n, peaks->shifts, tol, prec, peaks->out,
-                            c->stream));
+      HIP_OK(c, launch_step(t->args, q, o, r->n_wg, *peaks, p.tol, p.prec, c->stream));
     else
       HIP_OK(c, launch_explain_scan(ta, q, o, r->n_wg, c->stream));
   }
   if (fused) return SST_OK;
   if (r->bitset_scan) {  // the expand kernel routes the windows the bitset scan queued
-    Prof p(c, SST_K_EXPLAIN_EXPAND);
+    Prof prof(c, SST_K_EXPLAIN_EXPAND);
     HIP_OK(c, launch_explain_expand(ta, q, o, r->n_expand_waves / (kWG / 64), c->stream));
     eager_tail = true;
   }
@@ -1298,13 +1312,46 @@ int alloc_result(sst_table* t, int64_t n, sst_result** out, bool step = false) {
   }
   if (!ok) {
     (void)hipGetLastError();
-    free_result_bufs(r);
-    delete r;
+    destroy_result(r);
     return fail(c, SST_E_NOMEM, "device allocation failed (result)");
   }
   *out = r;
   return SST_OK;
 }
+
+// An entry point's hold on the result it fills: the caller's (*out, reused
+// for another pass) or one allocated here.  A result allocated here is freed
+// again unless the call reaches commit(), which alone writes *out; a reused
+// one is never freed and stays the caller's, whatever the call returns.
+struct ResultLease {
+  sst_result* r = nullptr;
+  bool reuse = false;
+  sst_result** out = nullptr;
+  ResultLease() = default;
+  ResultLease(const ResultLease&) = delete;
+  ResultLease& operator=(const ResultLease&) = delete;
+  ~ResultLease() {
+    if (r && !reuse) destroy_result(r);
+  }
+  // n: the pass's queries (set_n: a reused result takes it as its n) or, for
+  // a pass that produces its own queries, the capacity it needs
+  int acquire(sst_table* t, sst_result** out_, int64_t n, bool step_grid, bool set_n) {
+    out = out_;
+    r = *out;
+    reuse = r != nullptr;
+    if (!reuse) return alloc_result(t, n, &r, step_grid);
+    if (r->ctx != t->ctx || n > r->cap_n)
+      return fail(t->ctx, SST_E_ARG,
+                  set_n ? "result reuse: other ctx or capacity < n" : "result reuse: other ctx or capacity");
+    if (set_n) r->n = n;
+    return SST_OK;
+  }
+  int commit() {
+    *out = r;
+    r = nullptr;
+    return SST_OK;
+  }
+};
 
 // Wait for the current pass's last pack to publish its header and read it.
 // The header lives in host-mapped memory, written by the pack kernel as soon
@@ -1379,10 +1426,8 @@ int settle(sst_result* r) {
     if (attempt == 6) return fail(c, SST_E_INTERNAL, "explain: retries exhausted");
     HIP_OK(c, hipStreamSynchronize(c->stream));  // the pack may still run: buffers are about to be replaced
     if (int rc = grow_for_retry(r, regions, spill, exact, h[kHdrCursor], h[kHdrRegionNeed])) return rc;
-    const auto p = r->pass;  // a copy: the pass rewrites it
-    if (int rc = explain_pass(p.t, r, p.mass, p.thr, p.mods, p.mods_scalar, p.tol, p.prec, p.with_memo, p.cap, true,
-                              nullptr, p.alpha, p.spec, &p.lb))
-      return rc;
+    const PassSpec p = r->pass;  // a copy: the pass rewrites it
+    if (int rc = explain_pass(r, p, true)) return rc;
     launched = true;
   }
   if (launched) {
@@ -1464,24 +1509,11 @@ int sst_explain_batch_device(sst_table* t, const double* d_mass, const double* d
   sst_ctx* c = t->ctx;
   std::lock_guard<std::recursive_mutex> g(c->mu);
   if (int rc = set_device(c)) return rc;
-  sst_result* r = *out;
-  const bool reuse = r != nullptr;
-  if (reuse) {
-    if (r->ctx != c || n > r->cap_n) return fail(c, SST_E_ARG, "result reuse: other ctx or capacity < n");
-    r->n = n;
-  } else if (int rc = alloc_result(t, n, &r)) {
-    return rc;
-  }
-  int rc = explain_pass(t, r, d_mass, d_thr, d_mods, mods_scalar, tol, prec, with_memo, cap_count, false);
-  if (rc) {
-    if (!reuse) {
-      free_result_bufs(r);
-      delete r;
-    }
-    return rc;
-  }
-  *out = r;
-  return SST_OK;
+  ResultLease res;
+  if (int rc = res.acquire(t, out, n, false, true)) return rc;
+  const PassSpec pass{t, d_mass, d_thr, d_mods, mods_scalar, tol, prec, with_memo, cap_count};
+  if (int rc = explain_pass(res.r, pass, false)) return rc;
+  return res.commit();
 }
 
 int sst_explain_alpha_batch_device(sst_table* t, const double* d_mass, const double* d_thr, const int32_t* d_spec,
@@ -1492,25 +1524,11 @@ int sst_explain_alpha_batch_device(sst_table* t, const double* d_mass, const dou
   sst_ctx* c = t->ctx;
   std::lock_guard<std::recursive_mutex> g(c->mu);
   if (int rc = set_device(c)) return rc;
-  sst_result* r = *out;
-  const bool reuse = r != nullptr;
-  if (reuse) {
-    if (r->ctx != c || n > r->cap_n) return fail(c, SST_E_ARG, "result reuse: other ctx or capacity < n");
-    r->n = n;
-  } else if (int rc = alloc_result(t, n, &r)) {
-    return rc;
-  }
-  int rc = explain_pass(t, r, d_mass, d_thr, d_mods, mods_scalar, tol, prec, with_memo, cap_count, false, nullptr,
-                        d_alpha, d_spec);
-  if (rc) {
-    if (!reuse) {
-      free_result_bufs(r);
-      delete r;
-    }
-    return rc;
-  }
-  *out = r;
-  return SST_OK;
+  ResultLease res;
+  if (int rc = res.acquire(t, out, n, false, true)) return rc;
+  const PassSpec pass{t, d_mass, d_thr, d_mods, mods_scalar, tol, prec, with_memo, cap_count, d_alpha, d_spec};
+  if (int rc = explain_pass(res.r, pass, false)) return rc;
+  return res.commit();
 }
 
 int sst_explain_alpha_lens_batch_device(sst_table* t, const double* d_mass, const double* d_thr, const int32_t* d_spec,
@@ -1548,34 +1566,22 @@ int sst_explain_alpha_lens_batch_device(sst_table* t, const double* d_mass, cons
     }
     never[L] = (uint32_t)(!any_mod ? u32max : (lim < 0 ? 0 : std::min(lim, u32max - 1) + 1));
   }
-  sst_result* r = *out;
-  const bool reuse = r != nullptr;
-  if (reuse) {
-    if (r->ctx != c || n > r->cap_n) return fail(c, SST_E_ARG, "result reuse: other ctx or capacity < n");
-    r->n = n;
-  } else if (int rc = alloc_result(t, n, &r)) {
-    return rc;
-  }
-  auto drop = [&](int rc) {
-    if (!reuse) {
-      free_result_bufs(r);
-      delete r;
-    }
-    return rc;
-  };
+  ResultLease res;
+  if (int rc = res.acquire(t, out, n, false, true)) return rc;
+  sst_result* const r = res.r;
   // the result's own copies (a retry of the pass reads them again); a reused
   // result's previous pass is settled by its consumer before it is reused
   if (!r->lb_caps.ensure(caps.size() * 4) || !r->lb_capz.ensure(capz.size() * 8) || !r->lb_never.ensure(never.size() * 4))
-    return drop(fail(c, SST_E_NOMEM, "device allocation failed (result)"));
+    return fail(c, SST_E_NOMEM, "device allocation failed (result)");
   if (hipMemcpy(r->lb_caps.p, caps.data(), caps.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(r->lb_capz.p, capz.data(), capz.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(r->lb_never.p, never.data(), never.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-    return drop(fail(c, SST_E_HIP, "hipMemcpy (per-query budgets)"));
-  LenBudgets lb{d_qlen, (const int32_t*)r->lb_caps.p, (const uint64_t*)r->lb_capz.p, (const uint32_t*)r->lb_never.p};
-  int rc = explain_pass(t, r, d_mass, d_thr, d_mods, 0, tol, prec, 1, cap_count, false, nullptr, d_alpha, d_spec, &lb);
-  if (rc) return drop(rc);
-  *out = r;
-  return SST_OK;
+    return fail(c, SST_E_HIP, "hipMemcpy (per-query budgets)");
+  const LenBudgets lb{d_qlen, (const int32_t*)r->lb_caps.p, (const uint64_t*)r->lb_capz.p,
+                      (const uint32_t*)r->lb_never.p};
+  const PassSpec pass{t, d_mass, d_thr, d_mods, 0, tol, prec, 1, cap_count, d_alpha, d_spec, lb};
+  if (int rc = explain_pass(r, pass, false)) return rc;
+  return res.commit();
 }
 
 int sst_step_device(sst_table* t, const double* d_obs, int64_t n_peaks, const double* shifts, int n_shifts,
@@ -1588,25 +1594,12 @@ int sst_step_device(sst_table* t, const double* d_obs, int64_t n_peaks, const do
   sst_ctx* c = t->ctx;
   std::lock_guard<std::recursive_mutex> g(c->mu);
   if (int rc = set_device(c)) return rc;
-  sst_result* r = *out;
-  const bool reuse = r != nullptr;
-  if (reuse) {
-    if (r->ctx != c || n > r->cap_n) return fail(c, SST_E_ARG, "result reuse: other ctx or capacity < n");
-    r->n = n;
-  } else if (int rc = alloc_result(t, n, &r, n_peaks > 0 && n_shifts > 0)) {
-    return rc;
-  }
+  ResultLease res;
+  if (int rc = res.acquire(t, out, n, n_peaks > 0 && n_shifts > 0, true)) return rc;
+  const PassSpec pass{t, d_mass, d_thr, d_mods, mods_scalar, tol, prec, with_memo, cap_count};
   const PeaksJob job{d_obs, n_peaks, shifts, n_shifts, d_valid_out};
-  int rc = explain_pass(t, r, d_mass, d_thr, d_mods, mods_scalar, tol, prec, with_memo, cap_count, false, &job);
-  if (rc) {
-    if (!reuse) {
-      free_result_bufs(r);
-      delete r;
-    }
-    return rc;
-  }
-  *out = r;
-  return SST_OK;
+  if (int rc = explain_pass(res.r, pass, false, &job)) return rc;
+  return res.commit();
 }
 
 int sst_step_rows_device(sst_table* t, const double* d_obs, const int64_t* d_peak_off, int64_t n_spec,
@@ -1633,20 +1626,9 @@ int sst_step_rows_device(sst_table* t, const double* d_obs, const int64_t* d_pea
     for (int r = 1; r < t->n_rows; ++r)
       if (t->is_mod[r] && t->cap[r] < 2) return fail(c, SST_E_ARG, "rows step: a modification cap < 2 can bind");
   }
-  sst_result* r = *out;
-  const bool reuse = r != nullptr;
-  if (reuse) {
-    if (r->ctx != c || max_queries > r->cap_n) return fail(c, SST_E_ARG, "result reuse: other ctx or capacity");
-  } else if (int rc = alloc_result(t, max_queries, &r)) {
-    return rc;
-  }
-  auto bail = [&](int rc) {
-    if (!reuse) {
-      free_result_bufs(r);
-      delete r;
-    }
-    return rc;
-  };
+  ResultLease res;  // n stays: the pass produces its queries (settle() reads their count from the header)
+  if (int rc = res.acquire(t, out, max_queries, false, false)) return rc;
+  sst_result* const r = res.r;
   const size_t P = (size_t)n_peaks, S = (size_t)n_spec;
   const size_t NC = (size_t)c->n_cu * 64;  // chunk capacity: >= the wave kernels' waves (launch_rows_step checks)
   const bool fresh = !r->rows_ctl.p;
@@ -1655,7 +1637,7 @@ int sst_step_rows_device(sst_table* t, const double* d_obs, const int64_t* d_pea
       !r->rows_side.ensure(2 * S * 4) || !r->rows_tot.ensure(3 * S * 4) || !r->rows_chunk.ensure((6 * NC + 6 * (NC / kRowsTile + 1)) * 8) ||
       !r->rows_big.ensure(S * 4) || !r->rows_redo.ensure(S * 4) || !r->rows_ctl.ensure(64) ||
       !r->rows_ans.ensure(128 * S * 8 + (2 * kRowsAnsPerPeak * P / 64 + 2 * S + 2) * 64 * 4) || !r->rows_aq.ensure(2 * S * 4))
-    return bail(fail(c, SST_E_NOMEM, "device allocation failed (rows step)"));
+    return fail(c, SST_E_NOMEM, "device allocation failed (rows step)");
   if (fresh) {
     HIP_OK(c, hipMemsetAsync(r->rows_ctl.p, 0, 64, c->stream));
     HIP_OK(c, hipMemsetAsync((uint64_t*)r->rows_chunk.p + 6 * NC, 0, 6 * (NC / kRowsTile + 1) * 8, c->stream));  // tile sums
@@ -1726,8 +1708,7 @@ int sst_step_rows_device(sst_table* t, const double* d_obs, const int64_t* d_pea
     HIP_OK(c, launch_rows_step(t->args, a, c->n_cu, scan_dyn_lds(t->args), c->stream));
   }
   r->rows_tile_par = a.tile_par;
-  *out = r;
-  return SST_OK;
+  return res.commit();
 }
 
 int sst_explain_batch(sst_table* t, const double* mass, const double* thr, int64_t n, double tol, double prec,
@@ -1737,30 +1718,17 @@ int sst_explain_batch(sst_table* t, const double* mass, const double* thr, int64
   std::lock_guard<std::recursive_mutex> g(c->mu);
   *out = nullptr;
   if (int rc = set_device(c)) return rc;
-  size_t nn = (size_t)std::max<int64_t>(n, 1);
-  if (!c->in_mass.ensure(nn * 8) || (thr && !c->in_thr.ensure(nn * 8)) || (mods && !c->in_mods.ensure(nn * 8)))
-    return fail(c, SST_E_NOMEM, "device allocation failed (staging)");
-  if (n) {
-    HIP_OK(c, hipMemcpyAsync(c->in_mass.p, mass, n * 8, hipMemcpyHostToDevice, c->stream));
-    if (thr) HIP_OK(c, hipMemcpyAsync(c->in_thr.p, thr, n * 8, hipMemcpyHostToDevice, c->stream));
-    if (mods) HIP_OK(c, hipMemcpyAsync(c->in_mods.p, mods, n * 8, hipMemcpyHostToDevice, c->stream));
-  }
-  const double* dm = (const double*)c->in_mass.p;
-  const double* dt = thr ? (const double*)c->in_thr.p : nullptr;
-  const int64_t* dmo = mods ? (const int64_t*)c->in_mods.p : nullptr;
-  sst_result* r = nullptr;
-  if (int rc = alloc_result(t, n, &r)) return rc;
-  int rc = explain_pass(t, r, dm, dt, dmo, mods_scalar, tol, prec, with_memo, cap_count, true);
-  if (!rc) rc = fetch(r);  // settles: retries with larger workspaces happen there
-  for (int64_t i = 0; !rc && i < n; ++i)
-    if (r->h_status[i] <= kStatusPending) rc = fail(c, SST_E_INTERNAL, "explain: query left unresolved (internal error)");
-  if (rc) {
-    free_result_bufs(r);
-    delete r;
-    return rc;
-  }
-  *out = r;
-  return SST_OK;
+  Staged s;
+  if (int rc = stage_inputs(c, mass, thr, mods, n, 0, &s)) return rc;
+  ResultLease res;
+  if (int rc = res.acquire(t, out, n, false, true)) return rc;
+  sst_result* const r = res.r;
+  const PassSpec pass{t, s.mass, s.thr, s.mods, mods_scalar, tol, prec, with_memo, cap_count};
+  if (int rc = explain_pass(r, pass, true)) return rc;
+  if (int rc = fetch(r)) return rc;  // settles: retries with larger workspaces happen there
+  for (int64_t i = 0; i < n; ++i)
+    if (r->h_status[i] <= kStatusPending) return fail(c, SST_E_INTERNAL, "explain: query left unresolved (internal error)");
+  return res.commit();
 }
 
 int sst_explain_recursion_batch(sst_table* t, const double* mass, const double* thr, int64_t n, double tol,
@@ -1771,23 +1739,17 @@ int sst_explain_recursion_batch(sst_table* t, const double* mass, const double* 
   std::lock_guard<std::recursive_mutex> g(c->mu);
   *out = nullptr;
   if (int rc = set_device(c)) return rc;
-  const size_t nn = (size_t)std::max<int64_t>(n, 1);
-  if (!c->in_mass.ensure(nn * 8) || (thr && !c->in_thr.ensure(nn * 8)) || (mods && !c->in_mods.ensure(nn * 8)))
-    return fail(c, SST_E_NOMEM, "device allocation failed (staging)");
-  if (n) {
-    HIP_OK(c, hipMemcpyAsync(c->in_mass.p, mass, n * 8, hipMemcpyHostToDevice, c->stream));
-    if (thr) HIP_OK(c, hipMemcpyAsync(c->in_thr.p, thr, n * 8, hipMemcpyHostToDevice, c->stream));
-    if (mods) HIP_OK(c, hipMemcpyAsync(c->in_mods.p, mods, n * 8, hipMemcpyHostToDevice, c->stream));
-  }
-  sst_result* r = nullptr;
-  if (int rc = alloc_result(t, n, &r)) return rc;
+  Staged s;
+  if (int rc = stage_inputs(c, mass, thr, mods, n, 0, &s)) return rc;
+  ResultLease res;
+  if (int rc = res.acquire(t, out, n, false, true)) return rc;
+  sst_result* const r = res.r;
   // no scan: the pack finds empty scan tallies and takes the kernel's hit
   // records and spill bytes
   HIP_OK(c, hipMemsetAsync(r->tally.p, 0, r->tally.bytes, c->stream));
   HIP_OK(c, hipMemsetAsync(r->wg_tally.p, 0, r->wg_tally.bytes, c->stream));
-  QueryArgs q{(const double*)c->in_mass.p, thr ? (const double*)c->in_thr.p : nullptr,
-              mods ? (const int64_t*)c->in_mods.p : nullptr, mods_scalar, n, tol, prec, 1.0 / prec, 1, cap_count,
-              kRecNodeBudget};
+  const QueryArgs q = query_args(PassSpec{t, s.mass, s.thr, s.mods, mods_scalar, tol, prec, 1, cap_count}, n, t->args,
+                                 kRecNodeBudget);
   // one 64-lane block per query in flight (k_explain_recursion<WAVE>), each
   // with its own memo slice
   int units = (int)std::min<int64_t>(256, n);
@@ -1844,13 +1806,8 @@ int sst_explain_recursion_batch(sst_table* t, const double* mass, const double* 
     r->settled = true;
     rc = fetch(r);
   }
-  if (rc) {
-    free_result_bufs(r);
-    delete r;
-    return rc;
-  }
-  *out = r;
-  return SST_OK;
+  if (rc) return rc;
+  return res.commit();
 }
 
 int sst_result_settle(sst_result* r, uint64_t* n_hits, uint64_t* payload_bytes) {
@@ -2044,8 +2001,7 @@ void sst_result_free(sst_result* r) {
   std::lock_guard<std::recursive_mutex> g(r->ctx->mu);
   (void)hipSetDevice(r->ctx->device);
   (void)hipStreamSynchronize(r->ctx->stream);
-  free_result_bufs(r);
-  delete r;
+  destroy_result(r);
 }
 
 int sst_result_stats(const sst_result* r, uint64_t* s) {
@@ -2125,18 +2081,11 @@ int sst_is_singleton_batch(sst_ctx* c, const int64_t* masses, int n_masses, cons
   std::lock_guard<std::recursive_mutex> g(c->mu);
   if (int rc = set_device(c)) return rc;
   if (n == 0) return SST_OK;
-  const size_t nn = (size_t)n;
-  if (!c->in_mass.ensure(nn * 8) || (thr && !c->in_thr.ensure(nn * 8)) || !c->out_valid.ensure(nn))
-    return fail(c, SST_E_NOMEM, "device allocation failed (staging)");
-  HIP_OK(c, hipMemcpyAsync(c->in_mass.p, mass, nn * 8, hipMemcpyHostToDevice, c->stream));
-  if (thr) HIP_OK(c, hipMemcpyAsync(c->in_thr.p, thr, nn * 8, hipMemcpyHostToDevice, c->stream));
-  if (int rc = sst_is_singleton_batch_device(c, masses, n_masses, (const double*)c->in_mass.p,
-                                             thr ? (const double*)c->in_thr.p : nullptr, n, tol, prec,
-                                             (int8_t*)c->out_valid.p))
+  Staged s;
+  if (int rc = stage_inputs(c, mass, thr, nullptr, n, n, &s)) return rc;
+  if (int rc = sst_is_singleton_batch_device(c, masses, n_masses, s.mass, s.thr, n, tol, prec, (int8_t*)c->out_valid.p))
     return rc;
-  HIP_OK(c, hipMemcpyAsync(out, c->out_valid.p, nn, hipMemcpyDeviceToHost, c->stream));
-  HIP_OK(c, hipStreamSynchronize(c->stream));
-  return SST_OK;
+  return unstage_valid(c, out, n);
 }
 
 // ---- per-spectrum reduced alphabets (sst_alpha.hip) --------------------

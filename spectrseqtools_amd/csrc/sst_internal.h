@@ -742,16 +742,21 @@ hipError_t launch_table_certify(int C, const void* packed, const int* w, int n_r
                                 unsigned long long* out, hipStream_t st);
 hipError_t launch_table_certify_last(int C, const void* packed, const int* w, int n_rows, int64_t n_cols,
                                      unsigned long long* out, hipStream_t st);
-hipError_t launch_is_valid(const uint64_t* valid, int64_t limit, int64_t full_lo, int64_t full_hi, int64_t first_reach,
-                           const double* mass, const double* thr, int64_t n, double tol, double prec, int8_t* out,
-                           hipStream_t st);
-hipError_t launch_is_valid_peaks(const uint64_t* valid, int64_t limit, int64_t full_lo, int64_t full_hi,
-                                 int64_t first_reach, const double* obs, int64_t n, const double* shifts, int n_w,
-                                 double tol, double prec, int8_t* out, hipStream_t st);
-// the pair scan with is_valid over peaks x 4 breakage weights in front of it, one launch (k_step)
-hipError_t launch_step(const TableArgs& t, const QueryArgs& q, const OutArgs& o, int n_blocks, const double* obs,
-                       int64_t n_peaks, const double* shifts4, double tol, double prec, int8_t* valid_out,
-                       hipStream_t st);
+hipError_t launch_is_valid(const TableArgs& t, const double* mass, const double* thr, int64_t n, double tol,
+                           double prec, int8_t* out, hipStream_t st);
+// is_valid over peaks x breakage weights (host pointer `shifts`): alone, or issued with an explain pass
+// (sst_step_device); out[k * n + i] answers peak i at weight k
+struct PeaksJob {
+  const double* obs;
+  int64_t n;
+  const double* shifts;
+  int n_shifts;
+  int8_t* out;
+};
+hipError_t launch_is_valid_peaks(const TableArgs& t, const PeaksJob& job, double tol, double prec, hipStream_t st);
+// the pair scan with is_valid over peaks x 4 breakage weights (job.n_shifts == 4) in front of it, one launch (k_step)
+hipError_t launch_step(const TableArgs& t, const QueryArgs& q, const OutArgs& o, int n_blocks, const PeaksJob& job,
+                       double tol, double prec, hipStream_t st);
 hipError_t launch_explain_scan(const TableArgs& t, const QueryArgs& q, const OutArgs& o, int n_blocks,
                                hipStream_t st);
 hipError_t launch_explain_expand(const TableArgs& t, const QueryArgs& q, const OutArgs& o, int n_blocks,

@@ -3921,26 +3921,26 @@ hipError_t launch_index(int C, const void* packed, int n_rows, int64_t ncols, in
   }
   return hipGetLastError();
 }
-hipError_t launch_is_valid(const uint64_t* valid, int64_t limit, int64_t full_lo, int64_t full_hi, int64_t first_reach,
-                           const double* mass, const double* thr, int64_t n, double tol, double prec, int8_t* out,
-                           hipStream_t st) {
+hipError_t launch_is_valid(const TableArgs& t, const double* mass, const double* thr, int64_t n, double tol,
+                           double prec, int8_t* out, hipStream_t st) {
   if (n <= 0) return hipSuccess;
   const int grid = (int)blocks_for(n, 256);
-  ValidArgs v{valid, limit, full_lo, full_hi, first_reach, mass, thr, n, tol, prec, 1.0 / prec, out};
+  ValidArgs v{t.valid, t.limit, t.full_lo, t.full_hi, t.first_reach, mass, thr, n, tol, prec, 1.0 / prec, out};
   if (thr)
     hipLaunchKernelGGL(k_is_valid<true>, dim3(grid), dim3(256), 0, st, v);
   else
     hipLaunchKernelGGL(k_is_valid<false>, dim3(grid), dim3(256), 0, st, v);
   return hipGetLastError();
 }
-hipError_t launch_is_valid_peaks(const uint64_t* valid, int64_t limit, int64_t full_lo, int64_t full_hi,
-                                 int64_t first_reach, const double* obs, int64_t n, const double* shifts, int n_w,
-                                 double tol, double prec, int8_t* out, hipStream_t st) {
+hipError_t launch_is_valid_peaks(const TableArgs& t, const PeaksJob& job, double tol, double prec, hipStream_t st) {
+  const int64_t n = job.n;
+  const int n_w = job.n_shifts;
   if (n <= 0 || n_w <= 0) return hipSuccess;
   const int grid = (int)blocks_for(n, 256);
-  ValidArgs v{valid, limit, full_lo, full_hi, first_reach, obs, nullptr, n, tol, prec, 1.0 / prec, out};
+  ValidArgs v{t.valid, t.limit, t.full_lo, t.full_hi, t.first_reach, job.obs, nullptr, n, tol, prec, 1.0 / prec,
+              job.out};
   PeakShifts sh{};  // 4 slots: the default branch below builds its own per group of 4
-  for (int k = 0; k < n_w && k < 4; ++k) sh.shift[k] = shifts[k];
+  for (int k = 0; k < n_w && k < 4; ++k) sh.shift[k] = job.shifts[k];
   switch (n_w) {  // the reference's breakage dicts: 4 weights (FULL_BREAKAGE_DICT: up to 16)
     case 1: hipLaunchKernelGGL(k_is_valid_peaks<1>, dim3(grid), dim3(256), 0, st, v, sh); break;
     case 2: hipLaunchKernelGGL(k_is_valid_peaks<2>, dim3(grid), dim3(256), 0, st, v, sh); break;
@@ -3950,9 +3950,9 @@ hipError_t launch_is_valid_peaks(const uint64_t* valid, int64_t limit, int64_t f
       for (int k0 = 0; k0 < n_w; k0 += 4) {  // four weights per launch, output block k0 on
         const int m = n_w - k0 < 4 ? n_w - k0 : 4;
         PeakShifts s2{};
-        for (int k = 0; k < m; ++k) s2.shift[k] = shifts[k0 + k];
+        for (int k = 0; k < m; ++k) s2.shift[k] = job.shifts[k0 + k];
         ValidArgs v2 = v;
-        v2.out = out + (size_t)k0 * n;
+        v2.out = job.out + (size_t)k0 * n;
         if (m == 4) hipLaunchKernelGGL(k_is_valid_peaks<4>, dim3(grid), dim3(256), 0, st, v2, s2);
         if (m == 3) hipLaunchKernelGGL(k_is_valid_peaks<3>, dim3(grid), dim3(256), 0, st, v2, s2);
         if (m == 2) hipLaunchKernelGGL(k_is_valid_peaks<2>, dim3(grid), dim3(256), 0, st, v2, s2);
@@ -3982,16 +3982,15 @@ hipError_t launch_explain_scan(const TableArgs& t, const QueryArgs& q, const Out
     hipLaunchKernelGGL((k_explain_scan<false, false>), dim3(n_blocks), dim3(kScanWG), dyn, st, a);
   return hipGetLastError();
 }
-hipError_t launch_step(const TableArgs& t, const QueryArgs& q, const OutArgs& o, int n_blocks, const double* obs,
-                       int64_t n_peaks, const double* shifts4, double tol, double prec, int8_t* valid_out,
-                       hipStream_t st) {
+hipError_t launch_step(const TableArgs& t, const QueryArgs& q, const OutArgs& o, int n_blocks, const PeaksJob& job,
+                       double tol, double prec, hipStream_t st) {
   if (!t.pairs_enabled || q.n <= 0) return hipErrorInvalidValue;
   const size_t dyn = scan_dyn_lds(t) + scan_hit_lds_bytes(o.lds_hits);
-  ValidArgs v{t.valid, t.limit, t.full_lo, t.full_hi, t.first_reach, obs, nullptr, n_peaks, tol, prec, 1.0 / prec,
-              valid_out};
+  ValidArgs v{t.valid, t.limit, t.full_lo, t.full_hi, t.first_reach, job.obs, nullptr, job.n, tol, prec, 1.0 / prec,
+              job.out};
   PeakShifts sh{};
-  for (int k = 0; k < 4; ++k) sh.shift[k] = shifts4[k];
-  const uint32_t a7 = (uint32_t)((n_peaks + kScanWG - 1) / kScanWG);
+  for (int k = 0; k < 4; ++k) sh.shift[k] = job.shifts[k];
+  const uint32_t a7 = (uint32_t)((job.n + kScanWG - 1) / kScanWG);
   const dim3 grid(a7 + (uint32_t)n_blocks);
   const StepArgs a{{t, q, o}, v, sh, a7};
   if (q.thr && q.max_mods)

@@ -362,3 +362,92 @@ def test_reuse_across_empty_pass_with_lookback(engine, dev, rows):
         cnt_, off_ = decode_hits(st_, hits_)
         assert canonical_digest(st_, cnt_, off_, pay_) == \
             canonical_digest(fresh.status, fresh.count, fresh.offset, fresh.payload)
+
+
+@pytest.mark.parametrize("entry", ["explain_device", "explain_alpha_device", "step_device"])
+def test_result_reuse_contract(engine, dev, rows, entry):
+    """The reuse contract of the device entry points: a pass of more queries
+    than the reused result's capacity is refused before anything is launched
+    and leaves the result as it was (n included); the result then takes
+    another batch and answers it as the host-buffer call does (the step's
+    is_valid bytes as is_valid_peaks).  Every device input holds 257 elements,
+    the refused size."""
+    torch = pytest.importorskip("torch")
+    from spectrseqtools_amd.pipeline import row_masks
+
+    rng = np.random.default_rng(19)
+    n, big, n_peaks = 256, 257, 64
+    batches = [_queries(rng, rows, big, 2) for _ in range(2)]
+    obs = np.sort(rng.uniform(150.0, 9000.0, n_peaks))
+    shifts = np.array([0.0, 375.183, 537.119, 912.303])
+    dev_t = torch.device("cuda", engine.device)
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev_t)
+
+    dd = [(up(m), up(t)) for m, t in batches]
+    ds = up(np.zeros(big, np.int32))
+    da = up(np.asarray(row_masks(np.array([[r > 0 for r in range(len(rows))]])), dtype=np.uint64).view(np.int64))
+    do = up(obs)
+    out7 = torch.full((len(shifts) * n_peaks,), 9, dtype=torch.int8, device=dev_t)
+    torch.cuda.synchronize()  # the engine queues on its own stream
+
+    def queue(batch, k, reuse):
+        dm, dt = dd[batch]
+        if entry == "explain_device":
+            return dev.explain_device(dm.data_ptr(), dt.data_ptr(), k, TOL, PREC, 10, reuse=reuse)
+        if entry == "explain_alpha_device":
+            return dev.explain_alpha_device(dm.data_ptr(), dt.data_ptr(), ds.data_ptr(), da.data_ptr(), k, TOL, PREC,
+                                            10, reuse=reuse)
+        return dev.step_device(do.data_ptr(), n_peaks, shifts, out7.data_ptr(), dm.data_ptr(), dt.data_ptr(), k, TOL,
+                               PREC, 10, reuse=reuse)
+
+    res = queue(0, n, None)
+    res.fetch_device()
+    with pytest.raises(_native.EngineError, match="result reuse"):
+        queue(0, big, res)
+    assert res.n == n
+    assert queue(1, n, res) is res
+    res.fetch_device()
+    masses, thr = batches[1]
+    _same(res, dev.explain(masses[:n], thr[:n], TOL, PREC, 10), n)
+    if entry == "step_device":
+        engine.synchronize()
+        assert np.array_equal(out7.cpu().numpy(), dev.is_valid_peaks(obs, shifts, TOL, PREC))
+
+
+def test_result_reuse_contract_rows_step(engine, dev):
+    """step_rows_device: a max_queries above the reused result's capacity is
+    refused, and the result still answers a following valid step (its
+    is_valid codes and every query as the host-built queries' explain)."""
+    torch = pytest.importorskip("torch")
+    from types import SimpleNamespace
+
+    import bench
+
+    wl = bench.build_workload(20, 9, SimpleNamespace(tolerance=TOL, precision=PREC, device_table=dev))
+    n = len(wl["a8_mass"])
+    cap = n + 64
+    dev_t = torch.device("cuda", engine.device)
+    do, dpo, dsu = (torch.from_numpy(wl[k]).to(dev_t) for k in ("obs", "peak_off", "su_seq"))
+    out7 = torch.full((4 * len(wl["obs"]),), 9, dtype=torch.int8, device=dev_t)
+    torch.cuda.synchronize()
+
+    def step(max_queries, reuse):
+        return dev.step_rows_device(do.data_ptr(), dpo.data_ptr(), 20, len(wl["obs"]), dsu.data_ptr(), wl["shifts"],
+                                    wl["sides"], out7.data_ptr(), wl["max_weight"], TOL, PREC, 10, max_queries,
+                                    reuse=reuse)
+
+    res = step(cap, None)
+    res.fetch_device()
+    assert res.n == n and n > 0
+    with pytest.raises(_native.EngineError, match="result reuse"):
+        step(cap + 1, res)
+    out7.fill_(9)
+    torch.cuda.synchronize()
+    assert step(cap, res) is res
+    res.fetch_device()
+    engine.synchronize()
+    assert res.n == n
+    assert np.array_equal(out7.cpu().numpy(), wl["a7_valid"])
+    _same(res, dev.explain(wl["a8_mass"], wl["a8_thr"], TOL, PREC, 10), n)
