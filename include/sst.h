@@ -1311,6 +1311,58 @@ typedef struct sst_final_args {
 uint64_t sst_final_max_combos(void);
 int sst_final_program_device(sst_table* t, const sst_final_args* a);
 
+/* The robust final program: the optimal sequence whatever subset of the
+ * optional fragments enters the program.  After filter_with_lp the final
+ * program runs over the fragments keep mode proves kept (R, required) plus the
+ * subset T the solver keeps of those it still has to decide (O, optional;
+ * prediction.py:126-166); the fragment set enters the program nowhere else.
+ * Everything not listed here is sst_final_program_device's definition.
+ *   frag_use: 0 unused, 1 required, 2 optional; NULL = all required; any other
+ *     value is treated as 1.
+ *   SKIPPED: its conditions apply to required and optional fragments alike;
+ *     the 16 384 limit counts both, so every total stays below 2^63.
+ *   The nine outputs of base: what sst_final_program_device writes for
+ *     frag_use' = (frag_use == 1), except that an optional fragment of a SOLVED
+ *     spectrum has iv and sum, its interval and sum under seq by the rule for
+ *     used fragments (smallest (l, r) among the minimisers, the empty one last).
+ *   With y* the first optimal y over R (seq), c*_j = c_j(y*) and
+ *     cap(y) = sum over R of c_j(y) + sum over O of min(c_j(y), c*_j),
+ *   five more outputs per spectrum, all 0 and rgap UINT64_MAX unless SOLVED:
+ *     n_optional (u32); cstar = sum over O of c*_j; rbest = min cap(y) over the
+ *     feasible y; rn_opt, the feasible y with cap(y) == rbest (u32,
+ *     saturating); rgap, the smallest cap above rbest minus rbest, UINT64_MAX
+ *     if there is none.  Without optional fragments cap == obj: cstar = 0,
+ *     rbest = best, rn_opt = n_opt, rgap = gap.
+ *   No limit on the number of optional fragments and no further status.  Every
+ *   output element is written on every call.
+ * What it proves.  With obj_T(y) = sum over R + T of c_j(y), for any y
+ *     min over T in O of [obj_T(y) - obj_T(y*)]
+ *       = sum_R (c_j(y) - c*_j) + sum_O min(0, c_j(y) - c*_j) = cap(y) - cap(y*),
+ *   and cap(y*) = best + cstar.  So y* is the unique minimiser of every obj_T
+ *   with margin m iff it is the unique minimiser of cap with margin m.  The
+ *   rounding argument of sst_final_program_device moves each objective by less
+ *   than one unit per fragment in the sum.  Hence if rbest == best + cstar,
+ *   rn_opt == 1 and rgap > 2 (n_used + n_optional), n_used the required
+ *   fragments, then for every T the program over R + T has the unique optimum
+ *   seq in real arithmetic (rn_opt == 1 with rbest == best + cstar already
+ *   implies n_opt == 1).  The caveats stay: completed solves only, for the
+ *   final solve and for the solves KEEP speaks about; iv is AN optimal x; no
+ *   solver runs here.  The criterion is sufficient, not necessary: it
+ *   quantifies over subsets a solver would never return.
+ * One kernel (k_final_robust, sst_final.hip: k_final_program's body with a
+ * second enumeration where a spectrum holds optional fragments) on the ctx
+ * stream; no scratch buffer, no global atomics.  Errors as
+ * sst_final_program_device; with n_spec > 0 the five pointers are non-NULL. */
+typedef struct sst_final_robust_args {
+  sst_final_args base;
+  uint32_t* n_optional;         /* outputs, [n_spec] each */
+  uint64_t* cstar;
+  uint64_t* rbest;
+  uint32_t* rn_opt;
+  uint64_t* rgap;
+} sst_final_robust_args;
+int sst_final_robust_device(sst_table* t, const sst_final_robust_args* a);
+
 /* compute_sequence_length_bound (mass_table.py:343-487) after the skeleton's
  * alphabet reduction (skeleton_building.py:315-336), both directions, for
  * queries on per-spectrum reduced alphabets, exact without a table rebuild:
@@ -1446,7 +1498,8 @@ int64_t sst_pyset_order(const int32_t* keys, const int64_t* hashes, int64_t n, i
 #define SST_K_ALIGN_KEEP 25 /* k_align_windows_keep (sst_align_windows_keep_device) */
 #define SST_K_ALIGN_SPLIT_KEEP 26 /* k_align_split_keep (sst_align_split_keep_device) */
 #define SST_K_FINAL 27 /* k_final_program (sst_final_program_device) */
-#define SST_K_COUNT 28
+#define SST_K_FINAL_ROBUST 28 /* k_final_robust (sst_final_robust_device) */
+#define SST_K_COUNT 29
 /* When enabled, every kernel launch of this ctx is bracketed by hipEvents
  * recorded on the ctx stream; sst_profile_read synchronises and returns the
  * summed milliseconds and launch counts per kernel id since the last read

@@ -42,7 +42,7 @@ EXPORTS = (
     "sst_align_capacity", "sst_align_windows_device", "sst_align_split_device",
     "sst_align_windows_caps_device", "sst_align_split_caps_device",
     "sst_align_windows_keep_device", "sst_align_split_keep_device",
-    "sst_final_max_combos", "sst_final_program_device",
+    "sst_final_max_combos", "sst_final_program_device", "sst_final_robust_device",
 )
 
 # kernel ids of sst_profile_read
@@ -58,7 +58,8 @@ K_ALIGN_SPLIT_CAPS = 24
 K_ALIGN_KEEP = 25
 K_ALIGN_SPLIT_KEEP = 26
 K_FINAL = 27
-K_COUNT = 28  # SST_K_COUNT
+K_FINAL_ROBUST = 28
+K_COUNT = 29  # SST_K_COUNT
 KERNEL_NAMES = {K_IS_VALID: "k_is_valid", K_EXPLAIN_SCAN: "k_explain_scan", K_EXPLAIN_DEEP: "k_explain_deferred",
                 K_EXPLAIN_EXPAND: "k_explain_expand",
                 K_RESULT_PACK: "k_result_pack",  # ids 3, 4: reserved (merged into the deferred launch)
@@ -69,7 +70,8 @@ KERNEL_NAMES = {K_IS_VALID: "k_is_valid", K_EXPLAIN_SCAN: "k_explain_scan", K_EX
                 K_HANDOFF: "k_handoff", K_TABLE_CERTIFY: "k_table_certify", K_ALIGN: "k_align_windows",
                 K_ALIGN_SPLIT: "k_align_split", K_ALIGN_CAPS: "k_align_windows_caps",
                 K_ALIGN_SPLIT_CAPS: "k_align_split_caps", K_ALIGN_KEEP: "k_align_windows_keep",
-                K_ALIGN_SPLIT_KEEP: "k_align_split_keep", K_FINAL: "k_final_program"}
+                K_ALIGN_SPLIT_KEEP: "k_align_split_keep", K_FINAL: "k_final_program",
+                K_FINAL_ROBUST: "k_final_robust"}
 
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
@@ -196,6 +198,13 @@ class FinalArgs(ctypes.Structure):
         [(n, ctypes.c_void_p) for n in ("row_mod", "mod_cap", "row_cap")] + \
         [("max_combos", ctypes.c_uint64)] + \
         [(n, ctypes.c_void_p) for n in ("status", "combos", "n_feas", "best", "n_opt", "gap", "seq", "iv", "sum")]
+
+
+class FinalRobustArgs(ctypes.Structure):
+    """The mirror of sst_final_robust_args (include/sst.h): sst_final_args by value, then the five robust outputs
+    (device pointers)."""
+    _fields_ = [("base", FinalArgs)] + \
+        [(n, ctypes.c_void_p) for n in ("n_optional", "cstar", "rbest", "rn_opt", "rgap")]
 
 
 # sst_final_program_device's status per spectrum (SST_FINAL_*)
@@ -419,6 +428,8 @@ def load_library(path=LIB_PATH):
     lib.sst_final_max_combos.restype = _U64
     lib.sst_final_program_device.argtypes = [_P, ctypes.POINTER(FinalArgs)]
     lib.sst_final_program_device.restype = _I
+    lib.sst_final_robust_device.argtypes = [_P, ctypes.POINTER(FinalRobustArgs)]
+    lib.sst_final_robust_device.restype = _I
     lib.sst_jaccard_device.argtypes = [_P, ctypes.POINTER(JaccardArgs)]
     lib.sst_jaccard_device.restype = _I
     lib.sst_skeleton_alpha_device.argtypes = [_P, _I64, _P, _P, _P, _P, _P]

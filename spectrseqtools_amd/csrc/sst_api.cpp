@@ -3699,29 +3699,51 @@ extern "C" int sst_align_split_keep_device(sst_table* t, const sst_align_args* a
 
 extern "C" uint64_t sst_final_max_combos(void) { return SST_FINAL_MAX_COMBOS; }
 
-extern "C" int sst_final_program_device(sst_table* t, const sst_final_args* a) {
-  if (!t) return SST_E_ARG;
-  if (!a) return fail(t->ctx, SST_E_ARG, std::string(__func__) + ": a NULL sst_final_args");
-  if (a->n_spec < 0 || a->n_spec > INT32_MAX) return fail(t->ctx, SST_E_ARG, std::string(__func__) + ": n_spec");
+// the argument checks of the final program's two entry points; SST_OK: launch (n_spec > 0)
+static int final_check(sst_table* t, const sst_final_args* a, const char* who) {
+  if (a->n_spec < 0 || a->n_spec > INT32_MAX) return fail(t->ctx, SST_E_ARG, std::string(who) + ": n_spec");
   if (!std::isfinite(a->prec) || !(a->prec > 0))
-    return fail(t->ctx, SST_E_ARG, std::string(__func__) + ": prec is not a positive finite number");
+    return fail(t->ctx, SST_E_ARG, std::string(who) + ": prec is not a positive finite number");
   if (a->max_combos == 0 || a->max_combos > SST_FINAL_MAX_COMBOS)
-    return fail(t->ctx, SST_E_ARG, std::string(__func__) + ": max_combos outside [1, sst_final_max_combos()]");
+    return fail(t->ctx, SST_E_ARG, std::string(who) + ": max_combos outside [1, sst_final_max_combos()]");
   if (a->n_spec == 0) return SST_OK;
   // (frag_use may be NULL: every fragment is used)
   if (!a->seq_len || !a->pos_off || !a->skeleton || !a->alpha || !a->frag_off || !a->frag_code || !a->frag_su ||
       !a->frag_min_end || !a->frag_max_end || !a->row_mod || !a->mod_cap || !a->row_cap || !a->status || !a->combos ||
       !a->n_feas || !a->best || !a->n_opt || !a->gap || !a->seq || !a->iv || !a->sum)
-    return fail(t->ctx, SST_E_ARG, std::string(__func__) + ": a NULL member of sst_final_args");
-  if (t->n_rows > SST_MAX_ROWS) return fail(t->ctx, SST_E_ARG, std::string(__func__) + ": more than SST_MAX_ROWS rows");
+    return fail(t->ctx, SST_E_ARG, std::string(who) + ": a NULL member of sst_final_args");
+  if (t->n_rows > SST_MAX_ROWS) return fail(t->ctx, SST_E_ARG, std::string(who) + ": more than SST_MAX_ROWS rows");
   for (int r = 0; r < t->n_rows; ++r)  // sums of 253 positions stay below 2^32
     if (t->masses[r] < 0 || t->masses[r] >= (int64_t)(0x100000000ull / 253))
-      return fail(t->ctx, SST_E_ARG, std::string(__func__) + ": a row mass outside [0, 2^32 / 253)");
+      return fail(t->ctx, SST_E_ARG, std::string(who) + ": a row mass outside [0, 2^32 / 253)");
+  return SST_OK;
+}
+
+extern "C" int sst_final_program_device(sst_table* t, const sst_final_args* a) {
+  if (!t) return SST_E_ARG;
+  if (!a) return fail(t->ctx, SST_E_ARG, std::string(__func__) + ": a NULL sst_final_args");
+  if (int e = final_check(t, a, __func__)) return e;
+  if (a->n_spec == 0) return SST_OK;
   sst_ctx* c = t->ctx;
   std::lock_guard<std::recursive_mutex> g(c->mu);
   if (int e = set_device(c)) return e;
   Prof p(c, SST_K_FINAL);
   HIP_OK(c, sst::launch_final(*a, t->args.w, t->n_rows, 3 * c->n_cu, c->stream));
+  return SST_OK;
+}
+
+extern "C" int sst_final_robust_device(sst_table* t, const sst_final_robust_args* a) {
+  if (!t) return SST_E_ARG;
+  if (!a) return fail(t->ctx, SST_E_ARG, std::string(__func__) + ": a NULL sst_final_robust_args");
+  if (int e = final_check(t, &a->base, __func__)) return e;
+  if (a->base.n_spec == 0) return SST_OK;
+  if (!a->n_optional || !a->cstar || !a->rbest || !a->rn_opt || !a->rgap)
+    return fail(t->ctx, SST_E_ARG, std::string(__func__) + ": a NULL member of sst_final_robust_args");
+  sst_ctx* c = t->ctx;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  if (int e = set_device(c)) return e;
+  Prof p(c, SST_K_FINAL_ROBUST);
+  HIP_OK(c, sst::launch_final_robust(*a, t->args.w, t->n_rows, 3 * c->n_cu, c->stream));
   return SST_OK;
 }
 

@@ -42,6 +42,15 @@
 // over positions write seq, threads over fragments walk the admissible intervals
 // in (l, r) order for iv and sum.  Every global store is a plain vector store of
 // an output element; no global atomics, no scratch buffer.
+//
+// The robust variant (k_final_robust, sst_final_robust_device: the same body, kRobust): frag_use 2 marks a fragment
+// the solver may still drop.  The enumeration above runs over the required fragments alone and gives y*; where the
+// spectrum holds optional fragments the prefix sums P* of y* go to LDS and the enumeration runs once more over all
+// used fragments, an optional one's cost capped at its cost under y* (c*_j, computed from P* by the thread that loads
+// its record, on every load: nothing is kept per optional fragment).  cap(y) - cap(y*) is the smallest of obj_T(y) -
+// obj_T(y*) over all subsets T of the optional fragments, so y* is the unique optimum of every obj_T iff it is of cap
+// (include/sst.h).  The capped costs are non-negative terms as the plain ones: bookkeeping, early stop and order are
+// the first pass's.  The extra LDS (caps, P*, two words) is an extension struct k_final_program does not instantiate.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -89,11 +98,33 @@ struct FinalLds {
 };
 static_assert(sizeof(FinalLds) <= 64 * 1024, "static LDS");
 
+// The robust variant's extension: k_final_program does not instantiate it.
+struct FinalRobustLds : FinalLds {
+  unsigned long long f_cap[kFinalF];  // a chunk's records: c*_j of an optional record, kNone64 of a required one
+  uint32_t pstar[256];                // P*(i): the prefix sums of y*, i in [0, L]
+  unsigned long long cstar;           // the sum of c*_j over the optional fragments
+  uint32_t n_optional;
+};
+static_assert(sizeof(FinalRobustLds) <= 54613, "three workgroups per CU (160 KiB of LDS)");
+
+template <bool kRobust>
+using FinalLdsOf = std::conditional_t<kRobust, FinalRobustLds, FinalLds>;
+
 struct FinalKArgs {
   sst_final_args a;
   const int* w;
   int n_rows;
 };
+
+struct FinalRobustKArgs {
+  sst_final_robust_args r;
+  const int* w;
+  int n_rows;
+};
+
+// which fragments a pass of the enumeration sums: every used one (k_final_program), the required ones (the robust
+// variant's first pass), every used one with the optional ones' costs capped (its second pass)
+enum { kPassAll = 0, kPassRequired = 1, kPassCapped = 2 };
 
 // A_i of position p: P_i & alpha where P_i != 0, else alpha; row 0 excluded (a0 / a1 hold rows 1 .. n_rows - 1 only)
 __device__ __forceinline__ void final_set(const uint64_t* skel, uint64_t a0, uint64_t a1, int p, uint64_t& m0,
@@ -132,28 +163,40 @@ __device__ __forceinline__ uint32_t final_prefix(const FinalLds& s, int i, int t
   return s.pbase[i] + s.D[s.kof[i]][tid];
 }
 
+// the prefix sums a cost is taken over: the lane's y, or y* (P* in LDS)
+struct FinalLanePrefix {
+  const FinalLds& s;
+  int tid;
+  __device__ __forceinline__ uint32_t operator()(int i) const { return final_prefix(s, i, tid); }
+};
+struct FinalStarPrefix {
+  const uint32_t* p;
+  __device__ __forceinline__ uint32_t operator()(int i) const { return p[i]; }
+};
+
 __device__ __forceinline__ uint64_t final_dist(int64_t q, uint32_t sum) {
   const int64_t d = q - (int64_t)((uint64_t)sum << 16);
   return (uint64_t)(d < 0 ? -d : d);
 }
 
-// c_j(y) of the lane's y
-__device__ __forceinline__ uint64_t final_cost(const FinalLds& s, int64_t q, uint32_t meta, int L, int tid) {
+// c_j(y) of the y whose prefix sums are P
+template <class Prefix>
+__device__ __forceinline__ uint64_t final_cost(const Prefix& P, int64_t q, uint32_t meta, int L) {
   const uint32_t cls = meta & 3u;
   const int lo = (int)((meta >> 8) & 0xffu), hi = (int)((meta >> 16) & 0xffu);
-  if (cls == 3) return final_dist(q, final_prefix(s, L, tid));
+  if (cls == 3) return final_dist(q, P(L));
   uint64_t best = kNone64;
   if (cls == 1) {
     for (int r = lo; r <= hi; ++r) {
-      const uint64_t c = final_dist(q, final_prefix(s, r + 1, tid));
+      const uint64_t c = final_dist(q, P(r + 1));
       best = c < best ? c : best;
     }
     return best;
   }
   if (cls == 2) {
-    const uint32_t total = final_prefix(s, L, tid);
+    const uint32_t total = P(L);
     for (int l = lo; l <= hi; ++l) {
-      const uint64_t c = final_dist(q, total - final_prefix(s, l, tid));
+      const uint64_t c = final_dist(q, total - P(l));
       best = c < best ? c : best;
     }
     return best;
@@ -161,17 +204,17 @@ __device__ __forceinline__ uint64_t final_cost(const FinalLds& s, int64_t q, uin
   if (q <= 0) return (uint64_t)(-q);  // every sum is >= 0: the empty interval
   // i <= j over P(0 .. L): the sum P(j) - P(i) grows with j and falls with i; the pointer that can still improve moves
   int i = 0, j = 0;
-  uint32_t pi = final_prefix(s, 0, tid), pj = pi;
+  uint32_t pi = P(0), pj = pi;
   for (;;) {
     const int64_t d = q - (int64_t)((uint64_t)(pj - pi) << 16);
     const uint64_t c = (uint64_t)(d < 0 ? -d : d);
     best = c < best ? c : best;
     if (d > 0) {
       if (j == L) break;
-      pj = final_prefix(s, ++j, tid);
+      pj = P(++j);
     } else {
       if (d == 0) break;
-      pi = final_prefix(s, ++i, tid);  // (d < 0 only where i < j, as q > 0)
+      pi = P(++i);  // (d < 0 only where i < j, as q > 0)
     }
   }
   return best;
@@ -217,22 +260,156 @@ __device__ __forceinline__ void final_write_unsolved(const sst_final_args& a, in
   }
 }
 
-__global__ __launch_bounds__(kFinalWG) void k_final_program(FinalKArgs k) {
-  __shared__ FinalLds s;
-  const sst_final_args& a = k.a;
-  const int tid = (int)threadIdx.x;
+// The robust outputs of spectrum g (one thread).
+__device__ __forceinline__ void final_write_robust(const sst_final_robust_args& r, int64_t g, uint32_t n_optional,
+                                                   uint64_t cstar, uint64_t rbest, uint32_t rn_opt, uint64_t rgap) {
+  r.n_optional[g] = n_optional;
+  r.cstar[g] = cstar;
+  r.rbest[g] = rbest;
+  r.rn_opt[g] = rn_opt;
+  r.rgap[g] = rgap;
+}
 
-  for (int r = tid; r < SST_MAX_ROWS + 8; r += kFinalWG) s.w[r] = r < k.n_rows ? (uint32_t)k.w[r] : 0u;
+// A spectrum that is not SOLVED, the robust outputs included: 0, and rgap UINT64_MAX.
+template <bool kRobust>
+__device__ __forceinline__ void final_unsolved(const sst_final_args& a, const sst_final_robust_args* rb, int tid,
+                                               int64_t g, uint8_t status, uint64_t combos, int64_t pos0, int64_t n_pos,
+                                               int64_t f0, int64_t nf_all) {
+  final_write_unsolved(a, g, status, combos, pos0, n_pos, f0, nf_all, tid);
+  if constexpr (kRobust)
+    if (tid == 0) final_write_robust(*rb, g, 0, 0, 0, 0, kNone64);
+}
+
+// Does the fragment at `at` enter this pass?
+template <int kPass>
+__device__ __forceinline__ bool final_in_pass(const uint8_t* use, int64_t at) {
+  if constexpr (kPass == kPassRequired) return !use || (use[at] && use[at] != 2);
+  return !use || use[at];
+}
+
+// One enumeration of the spectrum's y: every lane's (best, the smallest objective above it, count, first index,
+// feasible count) over the indices it takes.  kPassCapped: cst receives the c*_j of the optional records this
+// thread loaded (each record once: while base == 0).
+template <int kPass, class Lds>
+__device__ __forceinline__ void final_enumerate(Lds& s, const sst_final_args& a, int64_t f0, int64_t nf_all, int L,
+                                                uint64_t combos, int n_free, int fixed_mod, int mod_cap, int tid,
+                                                uint64_t& best, uint64_t& next, uint32_t& count, uint32_t& first_at,
+                                                uint32_t& feas, uint64_t& cst) {
+  const int n_chunks = (int)((nf_all + kFinalF - 1) / kFinalF);
+  for (uint32_t base = 0; base < (uint32_t)combos; base += kFinalWG) {
+    const uint32_t idx = base + (uint32_t)tid;
+    bool ok = idx < (uint32_t)combos;
+    if (ok) ok = fixed_mod + final_decode(s, idx, n_free, tid, false) <= mod_cap;
+    uint64_t obj = 0;
+    bool live = ok;  // the objective is still summed
+    for (int c = n_chunks - 1; c >= 0; --c) {  // (the last fragments first: see below)
+      const int nf = (int)(nf_all - (int64_t)c * kFinalF < kFinalF ? nf_all - (int64_t)c * kFinalF : kFinalF);
+      if (n_chunks > 1 || base == 0) {
+        __syncthreads();  // the previous chunk's records are no longer read
+        for (int j = tid; j < nf; j += kFinalWG) {
+          const int64_t at = f0 + (int64_t)c * kFinalF + j;
+          int64_t q = 0;
+          uint32_t meta = 4u;
+          if (final_in_pass<kPass>(a.frag_use, at)) {  // (a used fragment is within the model: checked above)
+            final_qfix(a.frag_su[at], a.prec, q);
+            final_meta(a.frag_code[at], a.frag_min_end[at], a.frag_max_end[at], L, meta);
+          }
+          s.f_q[j] = q;
+          s.f_meta[j] = meta;
+          if constexpr (kPass == kPassCapped) {
+            uint64_t cap = kNone64;
+            if (a.frag_use && a.frag_use[at] == 2) {  // c*_j again on every load: nothing is kept per fragment
+              cap = final_cost(FinalStarPrefix{s.pstar}, q, meta, L);
+              if (base == 0) cst += cap;
+            }
+            s.f_cap[j] = cap;
+          }
+        }
+        __syncthreads();
+      }
+      // from the last record down: the hand-off's order is ascending su, and the heavy fragments tell the y apart
+      if (live)
+        for (int j = nf - 1; j >= 0 && live; --j) {
+          const uint32_t meta = s.f_meta[j];
+          if (meta & 4u) continue;
+          if constexpr (kPass == kPassCapped) {
+            const uint64_t cost = final_cost(FinalLanePrefix{s, tid}, s.f_q[j], meta, L), cap = s.f_cap[j];
+            obj += cost < cap ? cost : cap;
+          } else {
+            obj += final_cost(FinalLanePrefix{s, tid}, s.f_q[j], meta, L);
+          }
+          live = obj <= next;  // costs only add: above the lane's two smallest objectives y changes no output
+        }
+    }
+    if (ok) ++feas;
+    if (live) {
+      if (obj < best) {
+        next = best;
+        best = obj;
+        count = 1;
+        first_at = idx;
+      } else if (obj == best) {
+        ++count;
+      } else if (obj < next) {
+        next = obj;
+      }
+    }
+  }
+}
+
+// The workgroup's record from the lanes': r_best[0], r_next[0], r_count[0], r_first[0], r_feas[0].
+__device__ __forceinline__ void final_reduce(FinalLds& s, int tid, uint64_t best, uint64_t next, uint32_t count,
+                                             uint32_t first_at, uint32_t feas) {
+  s.r_best[tid] = best;
+  s.r_next[tid] = next;
+  s.r_count[tid] = count;
+  s.r_first[tid] = first_at;
+  s.r_feas[tid] = feas;
+  __syncthreads();
+  for (int stride = kFinalWG / 2; stride > 0; stride >>= 1) {
+    if (tid < stride) {
+      const uint64_t b1 = s.r_best[tid], b2 = s.r_best[tid + stride];
+      const uint64_t n1 = s.r_next[tid], n2 = s.r_next[tid + stride];
+      const uint32_t i1 = s.r_first[tid], i2 = s.r_first[tid + stride];
+      s.r_feas[tid] += s.r_feas[tid + stride];
+      if (b1 == b2) {
+        s.r_next[tid] = n1 < n2 ? n1 : n2;
+        s.r_count[tid] += s.r_count[tid + stride];
+        s.r_first[tid] = i1 < i2 ? i1 : i2;
+      } else if (b1 < b2) {
+        s.r_next[tid] = n1 < b2 ? n1 : b2;
+      } else {
+        s.r_best[tid] = b2;
+        s.r_next[tid] = n2 < b1 ? n2 : b1;
+        s.r_count[tid] = s.r_count[tid + stride];
+        s.r_first[tid] = i2;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// The kernel body.  kRobust (k_final_robust, sst_final_robust_device): frag_use 2 marks an optional fragment; the
+// first enumeration runs over the required fragments alone, and where the spectrum holds optional ones a second one
+// runs over all of them with every optional cost capped at its cost under y* (include/sst.h).  rb: the five robust
+// outputs (kRobust only).
+template <bool kRobust, class KArgs>
+__device__ __forceinline__ void final_body(FinalLdsOf<kRobust>& s, const KArgs& k, const sst_final_args& a,
+                                           const sst_final_robust_args* rb) {
+  const int tid = (int)threadIdx.x;
+  const int n_rows = k.n_rows;
+
+  for (int r = tid; r < SST_MAX_ROWS + 8; r += kFinalWG) s.w[r] = r < n_rows ? (uint32_t)k.w[r] : 0u;
   uint64_t rows0 = ~1ull, rows1 = ~0ull;
-  if (k.n_rows < 64) {
-    rows0 &= (1ull << k.n_rows) - 1;
+  if (n_rows < 64) {
+    rows0 &= (1ull << n_rows) - 1;
     rows1 = 0;
-  } else if (k.n_rows < 128) {
-    rows1 = (1ull << (k.n_rows - 64)) - 1;
+  } else if (n_rows < 128) {
+    rows1 = (1ull << (n_rows - 64)) - 1;
   }
   if (tid < 2) s.mod[tid] = 0;
   __syncthreads();
-  for (int r = 1 + tid; r < k.n_rows && r < 128; r += kFinalWG)
+  for (int r = 1 + tid; r < n_rows && r < 128; r += kFinalWG)
     if (a.row_mod[r]) atomicOr(&s.mod[r >> 6], 1ull << (r & 63));
   __syncthreads();
   const uint64_t mod0 = s.mod[0], mod1 = s.mod[1];
@@ -241,12 +418,12 @@ __global__ __launch_bounds__(kFinalWG) void k_final_program(FinalKArgs k) {
     const int64_t f0 = a.frag_off[g], nf_all = a.frag_off[g + 1] - f0;
     const int64_t pos0 = a.pos_off[g], n_pos = a.pos_off[g + 1] - pos0;
     if (nf_all <= 0) {  // a default spectrum, or one without fragments: nothing is computed
-      final_write_unsolved(a, g, SST_FINAL_NONE, 0, pos0, n_pos, f0, 0, tid);
+      final_unsolved<kRobust>(a, rb, tid, g, SST_FINAL_NONE, 0, pos0, n_pos, f0, 0);
       continue;
     }
     const int L = a.seq_len[g];
     if (!(L >= 0 && L <= kFinalMaxLen && n_pos == (int64_t)L)) {
-      final_write_unsolved(a, g, SST_FINAL_SKIPPED, 0, pos0, n_pos, f0, nf_all, tid);
+      final_unsolved<kRobust>(a, rb, tid, g, SST_FINAL_SKIPPED, 0, pos0, n_pos, f0, nf_all);
       continue;
     }
     const uint64_t* skel = a.skeleton + 2 * pos0;
@@ -256,23 +433,27 @@ __global__ __launch_bounds__(kFinalWG) void k_final_program(FinalKArgs k) {
     if (tid == 0) {
       s.flags = 0;
       s.n_used = 0;
+      if constexpr (kRobust) s.n_optional = 0;
     }
     __syncthreads();
 
     // the used fragments: their number, and the conditions the model does not hold under
     {
-      uint32_t used = 0;
+      uint32_t used = 0, optional = 0;
       bool bad = false;
       for (int64_t j = tid; j < nf_all; j += kFinalWG) {
         const int64_t at = f0 + j;
         if (a.frag_use && !a.frag_use[at]) continue;
         ++used;
+        if constexpr (kRobust) optional += a.frag_use && a.frag_use[at] == 2;
         int64_t q;
         uint32_t meta;
         bad = bad || !final_qfix(a.frag_su[at], a.prec, q) ||
               !final_meta(a.frag_code[at], a.frag_min_end[at], a.frag_max_end[at], L, meta);
       }
       if (used) atomicAdd(&s.n_used, used);
+      if constexpr (kRobust)
+        if (optional) atomicAdd(&s.n_optional, optional);
       if (bad) atomicOr(&s.flags, 2u);
     }
     for (int p = tid; p < L; p += kFinalWG) {
@@ -285,11 +466,11 @@ __global__ __launch_bounds__(kFinalWG) void k_final_program(FinalKArgs k) {
     }
     __syncthreads();
     if ((s.flags & 2u) || s.n_used > kFinalMaxUsed) {
-      final_write_unsolved(a, g, SST_FINAL_SKIPPED, 0, pos0, n_pos, f0, nf_all, tid);
+      final_unsolved<kRobust>(a, rb, tid, g, SST_FINAL_SKIPPED, 0, pos0, n_pos, f0, nf_all);
       continue;
     }
     if (s.flags & 1u) {  // (combos = prod |A_i| = 0)
-      final_write_unsolved(a, g, SST_FINAL_INFEASIBLE, 0, pos0, n_pos, f0, nf_all, tid);
+      final_unsolved<kRobust>(a, rb, tid, g, SST_FINAL_INFEASIBLE, 0, pos0, n_pos, f0, nf_all);
       continue;
     }
 
@@ -333,7 +514,7 @@ __global__ __launch_bounds__(kFinalWG) void k_final_program(FinalKArgs k) {
       s.fixed_mod = fixed_mod;
     }
     // the row-free test: one row of alpha per thread, n_r counted over the positions' sets
-    for (int r = 1 + tid; r < k.n_rows; r += kFinalWG) {
+    for (int r = 1 + tid; r < n_rows; r += kFinalWG) {
       const uint64_t bit = 1ull << (r & 63);
       if (!((r < 64 ? a0 : a1) & bit)) continue;
       int n_r = 0;
@@ -342,102 +523,31 @@ __global__ __launch_bounds__(kFinalWG) void k_final_program(FinalKArgs k) {
         final_set(skel, a0, a1, p, m0, m1);
         n_r += ((r < 64 ? m0 : m1) & bit) != 0;
       }
-      const int cap = a.row_cap[(int64_t)L * k.n_rows + r];
+      const int cap = a.row_cap[(int64_t)L * n_rows + r];
       const bool modified = ((r < 64 ? mod0 : mod1) & bit) != 0;
       if (!(cap >= n_r || (modified && cap >= mod_cap))) atomicOr(&s.flags, 4u);
     }
     __syncthreads();
     const uint64_t combos = s.combos;
     if (s.flags & 4u) {
-      final_write_unsolved(a, g, SST_FINAL_NOT_FREE, combos, pos0, n_pos, f0, nf_all, tid);
+      final_unsolved<kRobust>(a, rb, tid, g, SST_FINAL_NOT_FREE, combos, pos0, n_pos, f0, nf_all);
       continue;
     }
     if (combos > a.max_combos) {
-      final_write_unsolved(a, g, SST_FINAL_TOO_LARGE, combos, pos0, n_pos, f0, nf_all, tid);
+      final_unsolved<kRobust>(a, rb, tid, g, SST_FINAL_TOO_LARGE, combos, pos0, n_pos, f0, nf_all);
       continue;
     }
 
     // the enumeration: combos <= 2^22, every free position is recorded
     const int n_free = (int)s.n_free, fixed_mod = s.fixed_mod;
-    const int n_chunks = (int)((nf_all + kFinalF - 1) / kFinalF);
-    uint64_t best = kNone64, next = kNone64;
+    uint64_t best = kNone64, next = kNone64, cst = 0;
     uint32_t count = 0, first_at = 0, feas = 0;
-    for (uint32_t base = 0; base < (uint32_t)combos; base += kFinalWG) {
-      const uint32_t idx = base + (uint32_t)tid;
-      bool ok = idx < (uint32_t)combos;
-      if (ok) ok = fixed_mod + final_decode(s, idx, n_free, tid, false) <= mod_cap;
-      uint64_t obj = 0;
-      bool live = ok;  // the objective is still summed
-      for (int c = n_chunks - 1; c >= 0; --c) {  // (the last fragments first: see below)
-        const int nf = (int)(nf_all - (int64_t)c * kFinalF < kFinalF ? nf_all - (int64_t)c * kFinalF : kFinalF);
-        if (n_chunks > 1 || base == 0) {
-          __syncthreads();  // the previous chunk's records are no longer read
-          for (int j = tid; j < nf; j += kFinalWG) {
-            const int64_t at = f0 + (int64_t)c * kFinalF + j;
-            int64_t q = 0;
-            uint32_t meta = 4u;
-            if (!a.frag_use || a.frag_use[at]) {  // (a used fragment is within the model: checked above)
-              final_qfix(a.frag_su[at], a.prec, q);
-              final_meta(a.frag_code[at], a.frag_min_end[at], a.frag_max_end[at], L, meta);
-            }
-            s.f_q[j] = q;
-            s.f_meta[j] = meta;
-          }
-          __syncthreads();
-        }
-        // from the last record down: the hand-off's order is ascending su, and the heavy fragments tell the y apart
-        if (live)
-          for (int j = nf - 1; j >= 0 && live; --j) {
-            const uint32_t meta = s.f_meta[j];
-            if (meta & 4u) continue;
-            obj += final_cost(s, s.f_q[j], meta, L, tid);
-            live = obj <= next;  // costs only add: above the lane's two smallest objectives y changes no output
-          }
-      }
-      if (ok) ++feas;
-      if (live) {
-        if (obj < best) {
-          next = best;
-          best = obj;
-          count = 1;
-          first_at = idx;
-        } else if (obj == best) {
-          ++count;
-        } else if (obj < next) {
-          next = obj;
-        }
-      }
-    }
-    s.r_best[tid] = best;
-    s.r_next[tid] = next;
-    s.r_count[tid] = count;
-    s.r_first[tid] = first_at;
-    s.r_feas[tid] = feas;
-    __syncthreads();
-    for (int stride = kFinalWG / 2; stride > 0; stride >>= 1) {
-      if (tid < stride) {
-        const uint64_t b1 = s.r_best[tid], b2 = s.r_best[tid + stride];
-        const uint64_t n1 = s.r_next[tid], n2 = s.r_next[tid + stride];
-        const uint32_t i1 = s.r_first[tid], i2 = s.r_first[tid + stride];
-        s.r_feas[tid] += s.r_feas[tid + stride];
-        if (b1 == b2) {
-          s.r_next[tid] = n1 < n2 ? n1 : n2;
-          s.r_count[tid] += s.r_count[tid + stride];
-          s.r_first[tid] = i1 < i2 ? i1 : i2;
-        } else if (b1 < b2) {
-          s.r_next[tid] = n1 < b2 ? n1 : b2;
-        } else {
-          s.r_best[tid] = b2;
-          s.r_next[tid] = n2 < b1 ? n2 : b1;
-          s.r_count[tid] = s.r_count[tid + stride];
-          s.r_first[tid] = i2;
-        }
-      }
-      __syncthreads();
-    }
+    final_enumerate<kRobust ? kPassRequired : kPassAll>(s, a, f0, nf_all, L, combos, n_free, fixed_mod, mod_cap, tid, best,
+                                                        next, count, first_at, feas, cst);
+    final_reduce(s, tid, best, next, count, first_at, feas);
     const uint32_t n_feas = s.r_feas[0];
     if (n_feas == 0) {
-      final_write_unsolved(a, g, SST_FINAL_INFEASIBLE, combos, pos0, n_pos, f0, nf_all, tid);
+      final_unsolved<kRobust>(a, rb, tid, g, SST_FINAL_INFEASIBLE, combos, pos0, n_pos, f0, nf_all);
       continue;
     }
     const uint32_t winner = s.r_first[0];
@@ -448,6 +558,29 @@ __global__ __launch_bounds__(kFinalWG) void k_final_program(FinalKArgs k) {
       a.best[g] = s.r_best[0];
       a.n_opt[g] = s.r_count[0];
       a.gap[g] = s.r_next[0] == kNone64 ? kNone64 : s.r_next[0] - s.r_best[0];
+    }
+    if constexpr (kRobust) {
+      const uint32_t n_optional = s.n_optional;
+      if (n_optional == 0) {  // cap == obj: the second enumeration would repeat the first
+        if (tid == 0)
+          final_write_robust(*rb, g, 0, 0, s.r_best[0], s.r_count[0],
+                             s.r_next[0] == kNone64 ? kNone64 : s.r_next[0] - s.r_best[0]);
+      } else {
+        // P*: every lane's column holds the winner's D
+        final_decode(s, winner, n_free, tid, false);
+        for (int i = tid; i <= L; i += kFinalWG) s.pstar[i] = final_prefix(s, i, tid);
+        if (tid == 0) s.cstar = 0;
+        __syncthreads();
+        best = next = kNone64;
+        count = first_at = feas = 0;
+        final_enumerate<kPassCapped>(s, a, f0, nf_all, L, combos, n_free, fixed_mod, mod_cap, tid, best, next, count,
+                                     first_at, feas, cst);
+        if (cst) atomicAdd(&s.cstar, (unsigned long long)cst);
+        final_reduce(s, tid, best, next, count, first_at, feas);
+        if (tid == 0)
+          final_write_robust(*rb, g, n_optional, s.cstar, s.r_best[0], s.r_count[0],
+                             s.r_next[0] == kNone64 ? kNone64 : s.r_next[0] - s.r_best[0]);
+      }
     }
     // the winner again: every lane's column holds its D
     final_decode(s, winner, n_free, tid, tid == 0);
@@ -519,6 +652,16 @@ __global__ __launch_bounds__(kFinalWG) void k_final_program(FinalKArgs k) {
   }
 }
 
+__global__ __launch_bounds__(kFinalWG) void k_final_program(FinalKArgs k) {
+  __shared__ FinalLds s;
+  final_body<false>(s, k, k.a, nullptr);
+}
+
+__global__ __launch_bounds__(kFinalWG) void k_final_robust(FinalRobustKArgs k) {
+  __shared__ FinalRobustLds s;
+  final_body<true>(s, k, k.r.base, &k.r);
+}
+
 }  // namespace
 
 hipError_t launch_final(const sst_final_args& a, const int* w, int n_rows, int n_wg, hipStream_t st) {
@@ -526,6 +669,14 @@ hipError_t launch_final(const sst_final_args& a, const int* w, int n_rows, int n
   const FinalKArgs k{a, w, n_rows};
   const unsigned grid = (unsigned)(a.n_spec < (int64_t)n_wg ? a.n_spec : (int64_t)n_wg);
   hipLaunchKernelGGL(k_final_program, dim3(grid), dim3(kFinalWG), 0, st, k);
+  return hipGetLastError();
+}
+
+hipError_t launch_final_robust(const sst_final_robust_args& r, const int* w, int n_rows, int n_wg, hipStream_t st) {
+  if (r.base.n_spec <= 0) return hipSuccess;
+  const FinalRobustKArgs k{r, w, n_rows};
+  const unsigned grid = (unsigned)(r.base.n_spec < (int64_t)n_wg ? r.base.n_spec : (int64_t)n_wg);
+  hipLaunchKernelGGL(k_final_robust, dim3(grid), dim3(kFinalWG), 0, st, k);
   return hipGetLastError();
 }
 

@@ -712,6 +712,8 @@ hipError_t launch_align(bool split, const sst_align_args& a, const sst_align_cap
                         const int* w, int n_rows, int n_wg, hipStream_t st);
 // the final program by exact enumeration (k_final_program, sst_final.hip): one spectrum per workgroup, n_wg workgroups
 hipError_t launch_final(const sst_final_args& a, const int* w, int n_rows, int n_wg, hipStream_t st);
+// the robust final program (k_final_robust, sst_final.hip): the same body with the second, capped enumeration
+hipError_t launch_final_robust(const sst_final_robust_args& r, const int* w, int n_rows, int n_wg, hipStream_t st);
 hipError_t launch_skel_alpha(int64_t n_spec, const int32_t* max_len, const uint64_t* skel_off, const uint64_t* skel,
                              const uint64_t* alpha, uint64_t canon0, uint64_t canon1, uint64_t* out, hipStream_t st);
 hipError_t launch_result_refs(const int8_t* status, int64_t n, const uint4* hits, uint64_t n_hits,

@@ -20,6 +20,14 @@ never reach the kernel.  final_decisions says where the enumeration's optimum
 is provably the program's (FINAL_TAKE) and where a solver still has to run
 (FINAL_SOLVE).  A solver stopped by its time limit may return anything; TAKE
 equals the reference under completed solves only.
+
+The robust final program (sst_final_robust_device; DESIGN "The robust final
+program") decides the FINAL_UNDECIDED spectra too: final_use(al, optional=True)
+marks the LP_SOLVE fragments optional, final_robust_host / final_robust_device
+enumerate once over the required fragments and once more with every optional
+cost capped at its cost under the first optimum (a RobustOutcome beside the
+FinalOutcome), and robust_decisions says where that optimum is provably the
+program's for every subset of the optional fragments the solver may keep.
 """
 import ctypes
 from dataclasses import dataclass
@@ -129,15 +137,64 @@ class FinalOutcome:
                    seq=np.zeros(n_pos, np.uint8), iv=np.full(nf, NO_INTERVAL, np.uint16), sum=np.zeros(nf, np.uint32))
 
 
-def final_use(al):
+@dataclass
+class RobustOutcome:
+    """The robust final program's five further results per spectrum, parallel
+    to a FinalOutcome (include/sst.h, sst_final_robust_device), as host arrays."""
+    n_optional: np.ndarray  # u32 optional fragments (0 unless SOLVED)
+    cstar: np.ndarray       # u64 sum over the optional fragments of their cost under seq
+    rbest: np.ndarray       # u64 min cap
+    rn_opt: np.ndarray      # u32 feasible y with cap == rbest
+    rgap: np.ndarray        # u64 smallest cap above rbest, minus rbest; NO_GAP if none
+
+    _DTYPES = {"n_optional": np.uint32, "cstar": np.uint64, "rbest": np.uint64, "rn_opt": np.uint32, "rgap": np.uint64}
+
+    def __post_init__(self):
+        for k, dt in self._DTYPES.items():
+            setattr(self, k, np.ascontiguousarray(getattr(self, k), dtype=dt))
+        if any(len(getattr(self, k)) != len(self.n_optional) for k in self._DTYPES):
+            raise ValueError("RobustOutcome: arrays of different lengths")
+
+    def __len__(self):
+        return len(self.n_optional)
+
+    def equals(self, other):
+        return all(np.array_equal(getattr(self, k), getattr(other, k)) for k in self._DTYPES)
+
+    def take(self, idx):
+        """The result of spectra idx, in that order (as FinalOutcome.take)."""
+        idx = np.asarray(idx, dtype=np.int64)
+        return RobustOutcome(**{k: getattr(self, k)[idx] for k in self._DTYPES})
+
+    @classmethod
+    def concat(cls, outcomes):
+        """Several results' spectra one after the other (as FinalOutcome.concat)."""
+        outcomes = list(outcomes)
+        if not outcomes:
+            raise ValueError("RobustOutcome.concat: nothing to concatenate")
+        return cls(**{k: np.concatenate([getattr(o, k) for o in outcomes]) for k in cls._DTYPES})
+
+    @classmethod
+    def blank(cls, outcome):
+        """The outputs of spectra that are not SOLVED, one per spectrum of `outcome`."""
+        S = len(outcome)
+        return cls(n_optional=np.zeros(S, np.uint32), cstar=np.zeros(S, np.uint64), rbest=np.zeros(S, np.uint64),
+                   rn_opt=np.zeros(S, np.uint32), rgap=np.full(S, NO_GAP, np.uint64))
+
+
+def final_use(al, optional=False):
     """(use, undecided) from a keep-mode AlignOutcome: use u8 per fragment, 1
     for the LP_KEEP fragments (filter_with_lp, run to optimality, keeps exactly
     those where nothing is LP_SOLVE); undecided bool per spectrum, True where
     some fragment is LP_SOLVE: the final program's fragment set is then the
-    solver's to decide."""
+    solver's to decide.  optional=True (the robust final program): use is also 2
+    at the LP_SOLVE fragments, and no spectrum is undecided."""
     if not al.has_keep:
         raise ValueError("final_use: the AlignOutcome is not in keep mode")
     dec = lp_decisions(al)
+    if optional:
+        use = np.where(dec == LP_KEEP, 1, np.where(dec == LP_SOLVE, 2, 0)).astype(np.uint8)
+        return use, np.zeros(len(al.frag_off) - 1, bool)
     solve = np.concatenate([[0], np.cumsum(dec == LP_SOLVE)])
     return (dec == LP_KEEP).astype(np.uint8), (solve[al.frag_off[1:]] - solve[al.frag_off[:-1]]) > 0
 
@@ -150,6 +207,19 @@ def final_decisions(fo, min_gap_units=0.5):
     unit is the margin of the DROP and KEEP sides); else FINAL_SOLVE."""
     need = np.maximum(2 * fo.n_used() + 1, int(np.ceil(min_gap_units * FIX))).astype(np.uint64)
     take = (fo.status == FINAL_SOLVED) & (fo.n_opt == 1) & (fo.gap >= need)
+    return np.where(take, FINAL_TAKE, FINAL_SOLVE).astype(np.uint8)
+
+
+def robust_decisions(fo, ro, min_gap_units=0.5):
+    """Per spectrum (u8) FINAL_TAKE where seq is provably the unique optimum,
+    with a margin, of the program over the required fragments plus ANY subset of
+    the optional ones: SOLVED, rbest == best + cstar (y* minimises cap), rn_opt
+    == 1 and rgap >= max(2 (n_used + n_optional) + 1, min_gap_units * 65536);
+    else FINAL_SOLVE.  fo, ro: final_robust_host's or final_robust_device's
+    (fo.n_used() counts the required and the optional fragments there).  Without
+    optional fragments this is final_decisions' answer."""
+    need = np.maximum(2 * fo.n_used() + 1, int(np.ceil(min_gap_units * FIX))).astype(np.uint64)
+    take = (fo.status == FINAL_SOLVED) & (ro.rbest == fo.best + ro.cstar) & (ro.rn_opt == 1) & (ro.rgap >= need)
     return np.where(take, FINAL_TAKE, FINAL_SOLVE).astype(np.uint8)
 
 
@@ -178,6 +248,16 @@ def _per_fragment(use, nf, who):
     return use
 
 
+def _per_fragment_robust(use, nf, who):
+    """use as 0 unused / 1 required / 2 optional (any other value: 1)."""
+    if use is None:
+        return np.ones(nf, np.uint8)
+    use = np.asarray(use).reshape(-1)
+    if len(use) != nf:
+        raise ValueError(f"{who}: use does not match the outcome's fragments")
+    return np.where(use == 0, 0, np.where(use == 2, 2, 1)).astype(np.uint8)
+
+
 def _per_spectrum(undecided, S, who):
     if undecided is None:
         return np.zeros(S, bool)
@@ -192,9 +272,12 @@ def _ends(cls, mn, mx):
     return min(mn, mx), (mx if cls == 1 else mn)
 
 
-def _solve_spectrum(L, sets, row_mass, row_mod, mod_cap, cls, qfix, mn, mx):
+def _solve_spectrum(L, sets, row_mass, row_mod, mod_cap, cls, qfix, mn, mx, in_obj=None, cap=None):
     """The enumeration of one modelled, row-free spectrum within max_combos:
-    (n_feas, best, n_opt, gap, seq, iv, sum); n_feas == 0: no feasible y."""
+    (n_feas, best, n_opt, gap, seq, iv, sum); n_feas == 0: no feasible y.
+    in_obj (bool per fragment, None: all): the fragments the objective sums; iv
+    and sum are given for every fragment.  cap (i64 per fragment, None: none):
+    a fragment's cost enters the objective as min(cost, cap)."""
     radices = [len(rows) for rows in sets]
     combos = int(np.prod(radices, dtype=object)) if L else 1
     mass = [np.array([int(row_mass[r]) for r in rows], dtype=np.int64) for rows in sets]
@@ -244,7 +327,10 @@ def _solve_spectrum(L, sets, row_mass, row_mod, mod_cap, cls, qfix, mn, mx):
         pairs = P[:, ib] - P[:, ia] if len(internal) else None
         obj = np.zeros(len(idx), np.int64)
         for j in range(len(cls)):
-            obj += costs(P, j, pairs)[0].min(axis=1)
+            if in_obj is not None and not in_obj[j]:
+                continue
+            c = costs(P, j, pairs)[0].min(axis=1)
+            obj += c if cap is None else np.minimum(c, cap[j])
         n_feas += len(idx)
         vals = np.unique(obj)
         for v in vals[:2].tolist():  # the block's smallest two distinct objectives
@@ -285,22 +371,40 @@ def final_host(outcome, precision, caps, row_cap, use=None, max_combos=FINAL_DEF
     caps = (row_mod, mod_cap) (alignment.lp_caps), row_cap the per-row caps
     table (alignment.lp_row_caps); use: u8 per fragment, None = all; undecided:
     bool per spectrum, those get FINAL_UNDECIDED and nothing is computed."""
-    max_combos = _check_max_combos(max_combos, "final_host")
-    S, nf = len(outcome), int(outcome.frag_off[-1])
+    use = _per_fragment(use, int(outcome.frag_off[-1]), "final_host")
+    return _final_host(outcome, precision, caps, row_cap, use, max_combos, undecided, "final_host")[0]
+
+
+def final_robust_host(outcome, precision, caps, row_cap, use=None, max_combos=FINAL_DEFAULT_COMBOS):
+    """The robust final program of every spectrum of `outcome` by the definition
+    (include/sst.h, sst_final_robust_device): (FinalOutcome, RobustOutcome).
+    use: u8 per fragment, 0 unused, 1 required, 2 optional (anything else: 1),
+    None = all required.  One enumeration over the required fragments (best,
+    n_opt, gap, seq: y*), then, where a spectrum holds optional fragments, a
+    second one over all of them with every optional cost capped at its cost
+    under y*.  The other arguments as final_host's."""
+    use = _per_fragment_robust(use, int(outcome.frag_off[-1]), "final_robust_host")
+    return _final_host(outcome, precision, caps, row_cap, use, max_combos, None, "final_robust_host")
+
+
+def _final_host(outcome, precision, caps, row_cap, use, max_combos, undecided, who):
+    """final_host (use in {0, 1}) and final_robust_host (use in {0, 1, 2}): (FinalOutcome, RobustOutcome)."""
+    max_combos = _check_max_combos(max_combos, who)
+    S = len(outcome)
     n_rows = len(outcome.row_mass)
     row_mod = np.ascontiguousarray(caps[0], dtype=np.uint8)
     mod_cap = np.ascontiguousarray(caps[1], dtype=np.int32)
     if len(row_mod) != n_rows or len(mod_cap) != S:
-        raise ValueError("final_host: caps do not match the outcome's rows / spectra")
+        raise ValueError(f"{who}: caps do not match the outcome's rows / spectra")
     row_cap = np.ascontiguousarray(row_cap, dtype=np.int32).reshape(-1)
     if len(row_cap) != (ALIGN_MAX_LEN + 1) * n_rows:
-        raise ValueError("final_host: row_cap is not a table of 254 lengths by the outcome's rows")
+        raise ValueError(f"{who}: row_cap is not a table of 254 lengths by the outcome's rows")
     row_cap = row_cap.reshape(ALIGN_MAX_LEN + 1, n_rows)
     if n_rows and (int(outcome.row_mass.min()) < 0 or int(outcome.row_mass.max()) >= (1 << 32) // ALIGN_MAX_LEN):
-        raise ValueError("final_host: a row mass outside [0, 2^32 / 253)")
-    use = _per_fragment(use, nf, "final_host")
-    undecided = _per_spectrum(undecided, S, "final_host")
+        raise ValueError(f"{who}: a row mass outside [0, 2^32 / 253)")
+    undecided = _per_spectrum(undecided, S, who)
     fo = FinalOutcome.blank(outcome)
+    ro = RobustOutcome.blank(outcome)
     with np.errstate(all="ignore"):
         u = np.asarray(outcome.frag_su, dtype=np.float64) / np.float64(precision)
         in_model = np.abs(u) < 2.0 ** 32  # (False for NaN and the infinities)
@@ -343,14 +447,20 @@ def final_host(outcome, precision, caps, row_cap, use=None, max_combos=FINAL_DEF
         if combos > max_combos:
             fo.status[g] = FINAL_TOO_LARGE
             continue
-        n_feas, best, n_opt, gap, seq, iv, sm = _solve_spectrum(L, sets, outcome.row_mass, row_mod, cap, cls, qfix[on],
-                                                                mn, mx)
+        optional = use[on] == 2
+        solve = (L, sets, outcome.row_mass, row_mod, cap, cls, qfix[on], mn, mx)
+        n_feas, best, n_opt, gap, seq, iv, sm = _solve_spectrum(*solve, in_obj=~optional if optional.any() else None)
         if n_feas == 0:
             fo.status[g] = FINAL_INFEASIBLE
             continue
         fo.status[g], fo.n_feas[g], fo.best[g], fo.n_opt[g], fo.gap[g] = FINAL_SOLVED, n_feas, best, n_opt, gap
         fo.seq[p], fo.iv[on], fo.sum[on] = seq, iv, sm
-    return fo
+        ro.rbest[g], ro.rn_opt[g], ro.rgap[g] = best, n_opt, gap
+        if optional.any():  # c*_j: the cost under y* (iv is a minimiser), the cap of the second enumeration
+            c_star = np.where(optional, np.abs(qfix[on] - FIX * sm.astype(np.int64)), np.iinfo(np.int64).max)
+            ro.n_optional[g], ro.cstar[g] = int(optional.sum()), int(c_star[optional].sum())
+            _, ro.rbest[g], ro.rn_opt[g], ro.rgap[g], _, _, _ = _solve_spectrum(*solve, cap=c_star)
+    return fo, ro
 
 
 def final_device(dp_table, outcome, use=None, max_combos=FINAL_DEFAULT_COMBOS, undecided=None, caps=None, row_cap=None):
@@ -362,20 +472,8 @@ def final_device(dp_table, outcome, use=None, max_combos=FINAL_DEFAULT_COMBOS, u
     final_host; undecided spectra are taken out before the upload."""
     from .pipeline_device import _one_stream
 
-    max_combos = _check_max_combos(max_combos, "final_device")
-    masses = [int(m.mass) for m in dp_table.masses]
-    if masses != [int(x) for x in outcome.row_mass]:
-        raise ValueError("final_device: the outcome is not on this table's rows")
+    max_combos, row_mod, mod_cap, row_cap = _device_inputs(dp_table, outcome, max_combos, caps, row_cap, "final_device")
     S, nf = len(outcome), int(outcome.frag_off[-1])
-    caps = lp_caps(dp_table, outcome) if caps is None else caps
-    row_mod = np.ascontiguousarray(caps[0], dtype=np.uint8)
-    mod_cap = np.ascontiguousarray(caps[1], dtype=np.int32)
-    if len(row_mod) != len(masses) or len(mod_cap) != S:
-        raise ValueError("final_device: caps do not match the table's rows / the outcome's spectra")
-    row_cap = lp_row_caps(dp_table, outcome) if row_cap is None else row_cap
-    row_cap = np.ascontiguousarray(row_cap, dtype=np.int32).reshape(-1)
-    if len(row_cap) != (ALIGN_MAX_LEN + 1) * len(masses):
-        raise ValueError("final_device: row_cap is not a table of 254 lengths by the table's rows")
     use = _per_fragment(use, nf, "final_device")
     undecided = _per_spectrum(undecided, S, "final_device")
     if not undecided.any():
@@ -393,7 +491,41 @@ def final_device(dp_table, outcome, use=None, max_combos=FINAL_DEFAULT_COMBOS, u
     return FinalOutcome.concat([part, FinalOutcome.blank(outcome.take(rest), FINAL_UNDECIDED)]).take(where)
 
 
-def _final_device(dp_table, o, use, row_mod, mod_cap, row_cap, max_combos):
+def final_robust_device(dp_table, outcome, use=None, max_combos=FINAL_DEFAULT_COMBOS, caps=None, row_cap=None):
+    """The robust final program of every spectrum of `outcome` on dp_table's
+    device (sst_final_robust_device): (FinalOutcome, RobustOutcome), with the
+    upload / launch / download shape of final_device.  use: as
+    final_robust_host's (0 unused, 1 required, 2 optional); caps, row_cap: as
+    final_device's."""
+    from .pipeline_device import _one_stream
+
+    max_combos, row_mod, mod_cap, row_cap = _device_inputs(dp_table, outcome, max_combos, caps, row_cap,
+                                                           "final_robust_device")
+    use = _per_fragment_robust(use, int(outcome.frag_off[-1]), "final_robust_device")
+    return _one_stream(_final_device)(dp_table, outcome, use, row_mod, mod_cap, row_cap, max_combos, robust=True)
+
+
+def _device_inputs(dp_table, outcome, max_combos, caps, row_cap, who):
+    """(max_combos, row_mod, mod_cap, row_cap) of a device call, checked against the table and the outcome."""
+    max_combos = _check_max_combos(max_combos, who)
+    masses = [int(m.mass) for m in dp_table.masses]
+    if masses != [int(x) for x in outcome.row_mass]:
+        raise ValueError(f"{who}: the outcome is not on this table's rows")
+    caps = lp_caps(dp_table, outcome) if caps is None else caps
+    row_mod = np.ascontiguousarray(caps[0], dtype=np.uint8)
+    mod_cap = np.ascontiguousarray(caps[1], dtype=np.int32)
+    if len(row_mod) != len(masses) or len(mod_cap) != len(outcome):
+        raise ValueError(f"{who}: caps do not match the table's rows / the outcome's spectra")
+    row_cap = lp_row_caps(dp_table, outcome) if row_cap is None else row_cap
+    row_cap = np.ascontiguousarray(row_cap, dtype=np.int32).reshape(-1)
+    if len(row_cap) != (ALIGN_MAX_LEN + 1) * len(masses):
+        raise ValueError(f"{who}: row_cap is not a table of 254 lengths by the table's rows")
+    return max_combos, row_mod, mod_cap, row_cap
+
+
+def _final_device(dp_table, o, use, row_mod, mod_cap, row_cap, max_combos, robust=False):
+    """One launch of sst_final_program_device (a FinalOutcome), or with robust of
+    sst_final_robust_device (a FinalOutcome and a RobustOutcome)."""
     import torch
 
     dt = dp_table.device_table
@@ -401,7 +533,7 @@ def _final_device(dp_table, o, use, row_mod, mod_cap, row_cap, max_combos):
     dev = torch.device("cuda", eng.device)
     S, nf, n_pos = len(o), int(o.frag_off[-1]), int(o.pos_off[-1])
     if S == 0:
-        return FinalOutcome.blank(o)
+        return (FinalOutcome.blank(o), RobustOutcome.blank(o)) if robust else FinalOutcome.blank(o)
 
     def up(x, dtype, n=1):  # (never an empty allocation: the entry point refuses NULL)
         x = np.ascontiguousarray(x, dtype=dtype).reshape(-1)
@@ -416,7 +548,10 @@ def _final_device(dp_table, o, use, row_mod, mod_cap, row_cap, max_combos):
     more = [up(row_mod, np.uint8), up(mod_cap, np.int32), up(row_cap, np.int32)]
     outs = [out(S, torch.uint8), out(S, torch.int64), out(S, torch.int64), out(S, torch.int64), out(S, torch.int32),
             out(S, torch.int64), out(n_pos, torch.uint8), out(nf, torch.int16), out(nf, torch.int32)]
-    a = _native.FinalArgs()
+    r_outs = [out(S, torch.int32), out(S, torch.int64), out(S, torch.int64), out(S, torch.int32),
+              out(S, torch.int64)] if robust else []
+    args = _native.FinalRobustArgs() if robust else _native.FinalArgs()
+    a = args.base if robust else args
     a.n_spec = S
     (a.seq_len, a.pos_off, a.skeleton, a.alpha, a.frag_off, a.frag_code, a.frag_su, a.frag_min_end, a.frag_max_end,
      a.frag_use) = (x.data_ptr() for x in ins)
@@ -424,11 +559,19 @@ def _final_device(dp_table, o, use, row_mod, mod_cap, row_cap, max_combos):
     a.row_mod, a.mod_cap, a.row_cap = (x.data_ptr() for x in more)
     a.max_combos = int(max_combos)
     a.status, a.combos, a.n_feas, a.best, a.n_opt, a.gap, a.seq, a.iv, a.sum = (x.data_ptr() for x in outs)
+    if robust:
+        args.n_optional, args.cstar, args.rbest, args.rn_opt, args.rgap = (x.data_ptr() for x in r_outs)
+    name = "sst_final_robust_device" if robust else "sst_final_program_device"
     torch.cuda.synchronize(dev)
-    eng.check(eng._lib.sst_final_program_device(dt.handle, ctypes.byref(a)), "sst_final_program_device")
+    eng.check(getattr(eng._lib, name)(dt.handle, ctypes.byref(args)), name)
     eng.synchronize()
     status, combos, n_feas, best, n_opt, gap, seq, iv, sm = (x.cpu().numpy() for x in outs)
-    return FinalOutcome(frag_off=np.array(o.frag_off, dtype=np.int64), pos_off=np.array(o.pos_off, dtype=np.int64),
-                        status=status[:S], combos=combos[:S].view(np.uint64), n_feas=n_feas[:S].view(np.uint64),
-                        best=best[:S].view(np.uint64), n_opt=n_opt[:S].view(np.uint32), gap=gap[:S].view(np.uint64),
-                        seq=seq[:n_pos], iv=iv[:nf].view(np.uint16), sum=sm[:nf].view(np.uint32))
+    fo = FinalOutcome(frag_off=np.array(o.frag_off, dtype=np.int64), pos_off=np.array(o.pos_off, dtype=np.int64),
+                      status=status[:S], combos=combos[:S].view(np.uint64), n_feas=n_feas[:S].view(np.uint64),
+                      best=best[:S].view(np.uint64), n_opt=n_opt[:S].view(np.uint32), gap=gap[:S].view(np.uint64),
+                      seq=seq[:n_pos], iv=iv[:nf].view(np.uint16), sum=sm[:nf].view(np.uint32))
+    if not robust:
+        return fo
+    n_optional, cstar, rbest, rn_opt, rgap = (x.cpu().numpy()[:S] for x in r_outs)
+    return fo, RobustOutcome(n_optional=n_optional.view(np.uint32), cstar=cstar.view(np.uint64),
+                             rbest=rbest.view(np.uint64), rn_opt=rn_opt.view(np.uint32), rgap=rgap.view(np.uint64))

@@ -1730,7 +1730,7 @@ def mirror_outcome(dp_table, obs, su_mass, seq_mass, max_len, breakage_dict, int
 def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=None, intensity=None,
               intensity_cutoff=0.5e6, mass_cutoff=50000, limits=DeviceLimits(), fallback="mirror", name_hash=None,
               trim=True, explanation_masses=None, record=None, align=False, align_split=False, align_caps=False,
-              align_keep=False, align_final=False, final_max_combos=None):
+              align_keep=False, align_final=False, final_max_combos=None, align_robust=False):
     """These spectra -> what Predictor.predict holds when it reaches its MILP
     stages (prediction.py:63-103), as a BatchOutcome: the six device stages
     (classify_device, fixpoint_device, bins_device, skeleton_device,
@@ -1787,7 +1787,13 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
     returns (BatchOutcome, AlignOutcome, FinalOutcome).  Spectra the device ran
     take final_device, mirror-routed ones final_host; final_max_combos (None:
     final_program.FINAL_DEFAULT_COMBOS) bounds the assignments enumerated per
-    spectrum.  The first two are what align_keep with align_split returns."""
+    spectrum.  The first two are what align_keep with align_split returns.
+    align_robust=True implies align_final and runs the robust final program
+    instead (final_program.final_use(optional=True): the LP_SOLVE fragments are
+    optional, no spectrum is FINAL_UNDECIDED); returns (BatchOutcome,
+    AlignOutcome, FinalOutcome, RobustOutcome).  Spectra the device ran take
+    final_robust_device, mirror-routed ones final_robust_host
+    (final_program.robust_decisions reads the pair)."""
     from .masses import EXPLANATION_MASSES, TOLERANCE
     from .pipeline import max_len_of
 
@@ -1862,6 +1868,7 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
                                frag_max_end=h["max_end"], breakage_names=names, row_names=dev_out.row_names,
                                row_mass=dev_out.row_mass)
     m_idx = np.flatnonzero(reason)
+    align_final = align_final or align_robust
     align_keep = align_keep or align_final
     align_split = align_split or align_final
     align_caps = align_caps or align_keep
@@ -1875,9 +1882,14 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
         from . import final_program
 
         combos = final_program.FINAL_DEFAULT_COMBOS if final_max_combos is None else final_max_combos
-        use, undecided = final_program.final_use(dev_al)
-        dev_fo = final_program.final_device(dp_table, dev_out, use=use, max_combos=combos, undecided=undecided)
+        use, undecided = final_program.final_use(dev_al, optional=align_robust)
+        if align_robust:
+            dev_fo, dev_ro = final_program.final_robust_device(dp_table, dev_out, use=use, max_combos=combos)
+        else:
+            dev_fo = final_program.final_device(dp_table, dev_out, use=use, max_combos=combos, undecided=undecided)
     if not len(m_idx):
+        if align_robust:
+            return dev_out, dev_al, dev_fo, dev_ro
         return (dev_out, dev_al, dev_fo) if align_final else (dev_out, dev_al) if align else dev_out
     mirrored = [mirror_outcome(dp_table, obs[offsets[g]:offsets[g + 1]], su_seq[g], seq_mass[g], max_len[g],
                                breakage_dict, None if inten is None else inten[offsets[g]:offsets[g + 1]],
@@ -1894,12 +1906,19 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
                 for o in mirrored]
         al = alignment.AlignOutcome.concat([dev_al] + m_al)
         if align_final:
-            m_fo = []
+            m_fo, m_ro = [], []
             for o, a in zip(mirrored, m_al):
-                use, undecided = final_program.final_use(a)
-                m_fo.append(final_program.final_host(o, dp_table.precision, alignment.lp_caps(dp_table, o),
-                                                     alignment.lp_row_caps(dp_table, o), use=use, max_combos=combos,
-                                                     undecided=undecided))
-            return both.take(where), al.take(where), final_program.FinalOutcome.concat([dev_fo] + m_fo).take(where)
+                use, undecided = final_program.final_use(a, optional=align_robust)
+                host_args = (o, dp_table.precision, alignment.lp_caps(dp_table, o), alignment.lp_row_caps(dp_table, o))
+                if align_robust:
+                    f, r = final_program.final_robust_host(*host_args, use=use, max_combos=combos)
+                    m_ro.append(r)
+                else:
+                    f = final_program.final_host(*host_args, use=use, max_combos=combos, undecided=undecided)
+                m_fo.append(f)
+            fo = final_program.FinalOutcome.concat([dev_fo] + m_fo).take(where)
+            if align_robust:
+                return both.take(where), al.take(where), fo, final_program.RobustOutcome.concat([dev_ro] + m_ro).take(where)
+            return both.take(where), al.take(where), fo
         return both.take(where), al.take(where)
     return both.take(where)

@@ -50,7 +50,7 @@ GPU-busy share of its wall time.
 
 Usage: python tools/pipeline_bench.py [--spectra 100000] [--seed 7] [--host-driven]
        [--backend nccl|gloo] [--dump-outcomes DIR] [--as-rank R] [--handoff [--handoff-repeats 3]]
-       [--align | --align-split] [--align-caps | --align-keep] [--align-final] [--modification-rate 0.5]
+       [--align | --align-split] [--align-caps | --align-keep] [--align-final] [--align-robust] [--modification-rate 0.5]
 """
 import argparse
 import json
@@ -388,6 +388,58 @@ def final_stage(dp, out, al, kernels, max_combos):
             "kernel_ms": {"k_final_program": kern.get("k_final_program", (0.0, 0))[0]}}
 
 
+def robust_stage(dp, out, al, kernels, max_combos):
+    """--align-robust: the robust final program (final_program.
+    final_robust_device) with the certificate's KEEP fragments required and its
+    LP_SOLVE fragments optional, so that no spectrum is left out.  Its seconds
+    run from the host arrays in to the host arrays out (uploads, k_final_robust,
+    downloads); it records the status shares, the TAKE share (robust_decisions)
+    over all spectra and over those with fragments, and among the spectra that
+    hold an LP_SOLVE fragment (UNDECIDED under --align-final): their TAKE share,
+    the share that fails each of the three conditions, and the distribution of
+    n_optional."""
+    from spectrseqtools_amd import final_program as fp
+
+    use, _ = fp.final_use(al, optional=True)
+    _, was_undecided = fp.final_use(al)
+    kernels()
+    t0 = time.perf_counter()
+    fo, ro = fp.final_robust_device(dp, out, use=use, max_combos=max_combos)
+    s = time.perf_counter() - t0
+    kern = kernels()
+    live = np.diff(out.frag_off) > 0
+    n_live = max(1, int(live.sum()))
+    dec = fp.robust_decisions(fo, ro)
+    solved = fo.status == fp.FINAL_SOLVED
+    need = np.maximum(2 * fo.n_used() + 1, fp.FIX // 2).astype(np.uint64)
+    open_solved = was_undecided & solved
+    share = lambda m, of: float(np.count_nonzero(m & of)) / max(1, int(of.sum()))  # noqa: E731
+    n_opt_of = ro.n_optional[open_solved]
+    return {"s": s, "spectra": int(len(fo)), "spectra_with_fragments": int(live.sum()), "max_combos": int(max_combos),
+            "required_fragments_share": float((use == 1).mean()) if len(use) else 0.0,
+            "optional_fragments_share": float((use == 2).mean()) if len(use) else 0.0,
+            "status_shares": fo.shares(),
+            "status_shares_with_fragments": {name: float(np.count_nonzero((fo.status == st) & live)) / n_live
+                                             for st, name in fp.STATUS_NAMES.items()},
+            "take_share": float(dec.mean()) if len(dec) else 0.0,
+            "take_share_with_fragments": float(dec[live].sum()) / n_live,
+            "take_share_of_solved": float(dec[solved].mean()) if solved.any() else 0.0,
+            "formerly_undecided": {
+                "spectra": int(was_undecided.sum()), "share_with_fragments": float((was_undecided & live).sum()) / n_live,
+                "status_shares": {name: share(fo.status == st, was_undecided) for st, name in fp.STATUS_NAMES.items()},
+                "take_share": share(dec == fp.FINAL_TAKE, was_undecided),
+                "take_share_of_solved": share(dec == fp.FINAL_TAKE, open_solved),
+                "of_solved_fails_rbest": share(ro.rbest != fo.best + ro.cstar, open_solved),
+                "of_solved_fails_rn_opt": share(ro.rn_opt != 1, open_solved),
+                "of_solved_fails_rgap": share(ro.rgap < need, open_solved),
+                "n_optional_counts": {str(int(k)): int(v) for k, v in zip(*np.unique(np.minimum(n_opt_of, 8),
+                                                                                   return_counts=True))},
+                "n_optional_max": int(n_opt_of.max(initial=0))},
+            "assignments_enumerated": int(fo.combos[solved].sum() + fo.combos[solved & (ro.n_optional > 0)].sum()),
+            "path": "device (sst_final_robust_device), host arrays in and out", "kernels": kern,
+            "kernel_ms": {"k_final_robust": kern.get("k_final_robust", (0.0, 0))[0]}}
+
+
 def align_stage(pd, dp, rows, ln, post, kernels, split=False, caps=False, keep=False, hold=None):
     """--align: the alignment certificate (alignment.align_device) over the
     hand-off of the spectra the stages ran -- wall seconds from the host
@@ -562,16 +614,22 @@ def main():
                     help="--align-keep --align-split, then the final program by exact enumeration (final_program."
                          "final_device) over the KEEP fragments: a stage \"final\" with its seconds, k_final_program's "
                          "time, the status and TAKE shares and the percentiles of log2(combos)")
+    ap.add_argument("--align-robust", action="store_true",
+                    help="--align-keep --align-split, then the robust final program (final_program.final_robust_device): "
+                         "the LP_SOLVE fragments are optional and no spectrum is UNDECIDED.  A stage \"final_robust\" "
+                         "with its seconds, k_final_robust's time, the status and TAKE shares, and the formerly "
+                         "undecided spectra's TAKE share, failed conditions and n_optional (n_optional_counts: 8 "
+                         "stands for 8 and more)")
     ap.add_argument("--final-max-combos", type=int, default=1 << 20,
-                    help="--align-final: assignments enumerated per spectrum at most (up to 2^22)")
+                    help="--align-final, --align-robust: assignments enumerated per spectrum at most (up to 2^22)")
     ap.add_argument("--modification-rate", type=float, default=0.5,
                     help="the sequences' universal modification rate: the synthetic spectra's and the table's "
                          "SequenceInformation's (0.05: the low-modification-rate variant)")
     ap.add_argument("--as-rank", type=int, default=None,
                     help="single process: generate the spectra rank R of a multi-rank run would get")
     args = ap.parse_args()
-    args.align_keep = args.align_keep or args.align_final
-    args.align_split = args.align_split or args.align_final
+    args.align_keep = args.align_keep or args.align_final or args.align_robust
+    args.align_split = args.align_split or args.align_final or args.align_robust
     args.align_caps = args.align_caps or args.align_keep
     args.align = args.align or args.align_split or args.align_caps
 
@@ -672,6 +730,8 @@ def main():
                         hold=held)
             if args.align_final:
                 final_stage(dp, held["outcome"], held["certificate"], lambda: {}, args.final_max_combos)
+            if args.align_robust:
+                robust_stage(dp, held["outcome"], held["certificate"], lambda: {}, args.final_max_combos)
         # the reach buffer at length_device's batch budget, as a serving
         # process holds it: the timed stage allocates nothing (its hipMalloc /
         # hipFree of tens of GB took 0.1-3 s from run to run)
@@ -851,6 +911,12 @@ def main():
             stages["final"]["s"] = tmax(stages["final"]["s"])
             busy(stages["final"])
             progress("final")
+        if args.align_robust:
+            barrier()
+            stages["final_robust"] = robust_stage(dp, held["outcome"], held["certificate"], kernels, args.final_max_combos)
+            stages["final_robust"]["s"] = tmax(stages["final_robust"]["s"])
+            busy(stages["final_robust"])
+            progress("final_robust")
     handoff = None
     if rows is not None and args.handoff:
         engine.profile(False)  # (the hand-off is timed by the wall clock alone, outside the stages)
