@@ -1363,6 +1363,88 @@ typedef struct sst_final_robust_args {
 } sst_final_robust_args;
 int sst_final_robust_device(sst_table* t, const sst_final_robust_args* a);
 
+/* The robust final program with the bounded search: spectra above max_combos
+ * are searched, not given up.  Everything not listed here is
+ * sst_final_robust_device's definition.
+ *   Arguments: robust (sst_final_robust_args); horizon H <= 2^62; max_width in
+ *     [1, SST_FINAL_SEARCH_MAX_WIDTH = sst_final_search_max_width()] (2^16: a
+ *     workgroup's two frontiers take 112 bytes of workspace per node of width);
+ *     three more outputs per spectrum: mode (u8), rounds (u32), nodes (u64).
+ *     robust.base.max_combos may be 0 here and only here: every modelled
+ *     spectrum is searched.  Otherwise it is within the existing limit.
+ *   Which path.  Precedence NONE, SKIPPED, an empty A_i, NOT_FREE as before.
+ *     Then a spectrum with combos <= max_combos is ENUMERATED: all fourteen
+ *     arrays are what sst_final_robust_device writes, mode = 1, rounds = nodes
+ *     = 0.  Otherwise it is SEARCHED, mode = 2 where SOLVED: more than
+ *     SST_FINAL_SEARCH_MAX_FREE = 48 free positions (|A_i| > 1) give TOO_LARGE;
+ *     then n_feas == 0 gives INFEASIBLE; a sweep that overflows (below) gives
+ *     TOO_LARGE.  A spectrum that is not SOLVED has mode = rounds = nodes = 0
+ *     and the unsolved defaults elsewhere.  combos is written as before.
+ *   n_feas of a searched spectrum: the number of feasible y, saturating at
+ *     UINT64_MAX, counted over the number of modified rows per position.
+ *   Nodes.  The free positions in position order are f_0 < ... < f_{n-1}.  A
+ *     node of depth d fixes one row at each of f_0 .. f_{d-1}.  It is
+ *     live-feasible iff the modified rows at the one-row positions, plus those
+ *     it fixed, plus one for every later free position all of whose rows are
+ *     modified, is at most mod_cap.  Children in ascending row order.  A leaf
+ *     (d = n) is a y; its index is the mixed-radix index of the definition.
+ *   Bound.  For a node, wmin_i = wmax_i = the row's mass at a fixed or one-row
+ *     position, the smallest and largest mass over A_i at an open one; Pmin,
+ *     Pmax their prefix sums.  For an interval [l, r]: Smin = Pmin(r + 1) -
+ *     Pmin(l), Smax likewise, d(l, r) = max(0, 65536 Smin - qfix_j, qfix_j -
+ *     65536 Smax); the empty interval: |qfix_j|.  lb_j(node) = min of d over
+ *     fragment j's admissible intervals; lb(node) = the sum over the required
+ *     fragments (pass 1), plus min(lb_j, c*_j) over the optional ones (pass
+ *     2).  Integers throughout.  lb(leaf) = obj(y) (cap(y) in pass 2); lb
+ *     never decreases from a node to its child; lb(node) is at most the
+ *     objective of every leaf below it.
+ *   Sweep(T).  S_0 = {root}; S_{d+1} = the live-feasible children c of S_d
+ *     with lb(c) <= T.  It OVERFLOWS iff some |S_d| > max_width.  Otherwise it
+ *     returns the leaves S_n: the feasible y with objective <= T (with n = 0
+ *     the root is the one leaf, whatever T).  Its node count: sum over d = 1 ..
+ *     n of |S_d|.
+ *   Pass 1 (required fragments).  T = max(H, 65536); run Sweep(T), and while it
+ *     returns no leaf T = 4 T, saturating at 2^63 - 1 (objectives stay below
+ *     2^63).  b = the smallest leaf objective; if b + H > T, one more
+ *     Sweep(b + H).  best = b; n_opt = the leaves with objective b, saturating
+ *     u32; seq = the one of them with the smallest index; gap = the smallest
+ *     leaf objective in (b, b + H] minus b, or H + 1 if there is none: gap =
+ *     min(true gap, H + 1), the only place a searched spectrum's outputs leave
+ *     the robust program's definition.  iv, sum, c*_j, cstar from seq as before.
+ *   Pass 2 (only where n_optional > 0): one Sweep(best + cstar + H) with the
+ *     capped bound (y* is a leaf of it).  rbest = the smallest leaf cap; rn_opt
+ *     = the leaves at rbest; rgap = the smallest leaf cap in (rbest, rbest + H]
+ *     minus rbest, or H + 1.  Without optional fragments the three copy best,
+ *     n_opt, gap.
+ *   rounds = the sweeps run in both passes, nodes = the sum of their counts; an
+ *     overflow in either pass makes the spectrum TOO_LARGE.  Every output is a
+ *     function of the inputs alone: S_d does not depend on an order of
+ *     evaluation, so identical calls give identical arrays, nodes included.
+ * Why the decisions stay sound.  A truncated gap never exceeds the true one, so
+ * final_decisions / robust_decisions read it unchanged: they say TAKE only
+ * where the true gap meets the need (at most 2 * 16 384 + 1 units or half a
+ * precision unit, below H + 1 at H = 2^17).
+ * Three launches on the ctx stream: k_final_robust (the enumerated spectra; the
+ * others come out TOO_LARGE), k_final_search_list (one workgroup: the list of
+ * those, and the three outputs' defaults), k_final_search (one workgroup per
+ * listed spectrum, a level's frontier ping-ponged in the context's workspace:
+ * cached across calls, freed by sst_ctx_trim).  Plain vector stores, no global
+ * atomics.  Errors as sst_final_robust_device, and SST_E_ARG with a message for
+ * max_width of 0 or above the limit, horizon > 2^62, a NULL mode / rounds /
+ * nodes with n_spec > 0; SST_E_NOMEM where the workspace cannot be had. */
+#define SST_FINAL_SEARCH_MAX_WIDTH (1u << 16)
+#define SST_FINAL_SEARCH_MAX_FREE 48
+typedef struct sst_final_search_args {
+  sst_final_robust_args robust;
+  uint64_t horizon;
+  uint32_t max_width;
+  uint8_t* mode;                /* outputs, [n_spec] each */
+  uint32_t* rounds;
+  uint64_t* nodes;
+} sst_final_search_args;
+uint32_t sst_final_search_max_width(void);
+int sst_final_search_device(sst_table* t, const sst_final_search_args* a);
+
 /* compute_sequence_length_bound (mass_table.py:343-487) after the skeleton's
  * alphabet reduction (skeleton_building.py:315-336), both directions, for
  * queries on per-spectrum reduced alphabets, exact without a table rebuild:
@@ -1499,7 +1581,8 @@ int64_t sst_pyset_order(const int32_t* keys, const int64_t* hashes, int64_t n, i
 #define SST_K_ALIGN_SPLIT_KEEP 26 /* k_align_split_keep (sst_align_split_keep_device) */
 #define SST_K_FINAL 27 /* k_final_program (sst_final_program_device) */
 #define SST_K_FINAL_ROBUST 28 /* k_final_robust (sst_final_robust_device) */
-#define SST_K_COUNT 29
+#define SST_K_FINAL_SEARCH 29 /* k_final_search_list / k_final_search (sst_final_search_device) */
+#define SST_K_COUNT 30
 /* When enabled, every kernel launch of this ctx is bracketed by hipEvents
  * recorded on the ctx stream; sst_profile_read synchronises and returns the
  * summed milliseconds and launch counts per kernel id since the last read

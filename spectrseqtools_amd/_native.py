@@ -43,6 +43,7 @@ EXPORTS = (
     "sst_align_windows_caps_device", "sst_align_split_caps_device",
     "sst_align_windows_keep_device", "sst_align_split_keep_device",
     "sst_final_max_combos", "sst_final_program_device", "sst_final_robust_device",
+    "sst_final_search_max_width", "sst_final_search_device",
 )
 
 # kernel ids of sst_profile_read
@@ -59,7 +60,8 @@ K_ALIGN_KEEP = 25
 K_ALIGN_SPLIT_KEEP = 26
 K_FINAL = 27
 K_FINAL_ROBUST = 28
-K_COUNT = 29  # SST_K_COUNT
+K_FINAL_SEARCH = 29
+K_COUNT = 30  # SST_K_COUNT
 KERNEL_NAMES = {K_IS_VALID: "k_is_valid", K_EXPLAIN_SCAN: "k_explain_scan", K_EXPLAIN_DEEP: "k_explain_deferred",
                 K_EXPLAIN_EXPAND: "k_explain_expand",
                 K_RESULT_PACK: "k_result_pack",  # ids 3, 4: reserved (merged into the deferred launch)
@@ -71,7 +73,7 @@ KERNEL_NAMES = {K_IS_VALID: "k_is_valid", K_EXPLAIN_SCAN: "k_explain_scan", K_EX
                 K_ALIGN_SPLIT: "k_align_split", K_ALIGN_CAPS: "k_align_windows_caps",
                 K_ALIGN_SPLIT_CAPS: "k_align_split_caps", K_ALIGN_KEEP: "k_align_windows_keep",
                 K_ALIGN_SPLIT_KEEP: "k_align_split_keep", K_FINAL: "k_final_program",
-                K_FINAL_ROBUST: "k_final_robust"}
+                K_FINAL_ROBUST: "k_final_robust", K_FINAL_SEARCH: "k_final_search"}
 
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
@@ -205,6 +207,13 @@ class FinalRobustArgs(ctypes.Structure):
     (device pointers)."""
     _fields_ = [("base", FinalArgs)] + \
         [(n, ctypes.c_void_p) for n in ("n_optional", "cstar", "rbest", "rn_opt", "rgap")]
+
+
+class FinalSearchArgs(ctypes.Structure):
+    """The mirror of sst_final_search_args (include/sst.h): sst_final_robust_args by value, the horizon, the width
+    and the three search outputs (device pointers)."""
+    _fields_ = [("robust", FinalRobustArgs), ("horizon", ctypes.c_uint64), ("max_width", ctypes.c_uint32)] + \
+        [(n, ctypes.c_void_p) for n in ("mode", "rounds", "nodes")]
 
 
 # sst_final_program_device's status per spectrum (SST_FINAL_*)
@@ -430,6 +439,10 @@ def load_library(path=LIB_PATH):
     lib.sst_final_program_device.restype = _I
     lib.sst_final_robust_device.argtypes = [_P, ctypes.POINTER(FinalRobustArgs)]
     lib.sst_final_robust_device.restype = _I
+    lib.sst_final_search_max_width.argtypes = []
+    lib.sst_final_search_max_width.restype = ctypes.c_uint32
+    lib.sst_final_search_device.argtypes = [_P, ctypes.POINTER(FinalSearchArgs)]
+    lib.sst_final_search_device.restype = _I
     lib.sst_jaccard_device.argtypes = [_P, ctypes.POINTER(JaccardArgs)]
     lib.sst_jaccard_device.restype = _I
     lib.sst_skeleton_alpha_device.argtypes = [_P, _I64, _P, _P, _P, _P, _P]

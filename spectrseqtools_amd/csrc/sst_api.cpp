@@ -96,6 +96,7 @@ struct sst_ctx {
     uint64_t done_q = 0, done_nodes = 0;
     double band_frac = 0.3;  // the largest band's share of a chunk's nodes seen so far
   } lbf, lbf_small;  // lbf_small: sst_length_bound_batch's (one table, few queries; 4 GB)
+  DevBuf final_search;  // the bounded search's list and frontiers (sst_final_search_device): kept across calls
   uint32_t hash_cap = 0;
   int exact_blocks = 0;
   int n_cu = 256;       // compute units (persistent grid sizing)
@@ -603,6 +604,7 @@ int sst_ctx_trim(sst_ctx* c) {
   HIP_OK(c, hipStreamSynchronize(c->stream));
   c->lbf = sst_ctx::LbfWs{};  // DevBuf frees on destruction
   c->lbf_small = sst_ctx::LbfWs{};
+  c->final_search.release();
   return SST_OK;
 }
 
@@ -3700,12 +3702,13 @@ extern "C" int sst_align_split_keep_device(sst_table* t, const sst_align_args* a
 extern "C" uint64_t sst_final_max_combos(void) { return SST_FINAL_MAX_COMBOS; }
 
 // the argument checks of the final program's two entry points; SST_OK: launch (n_spec > 0)
-static int final_check(sst_table* t, const sst_final_args* a, const char* who) {
+static int final_check(sst_table* t, const sst_final_args* a, const char* who, uint64_t least_combos = 1) {
   if (a->n_spec < 0 || a->n_spec > INT32_MAX) return fail(t->ctx, SST_E_ARG, std::string(who) + ": n_spec");
   if (!std::isfinite(a->prec) || !(a->prec > 0))
     return fail(t->ctx, SST_E_ARG, std::string(who) + ": prec is not a positive finite number");
-  if (a->max_combos == 0 || a->max_combos > SST_FINAL_MAX_COMBOS)
-    return fail(t->ctx, SST_E_ARG, std::string(who) + ": max_combos outside [1, sst_final_max_combos()]");
+  if (a->max_combos < least_combos || a->max_combos > SST_FINAL_MAX_COMBOS)
+    return fail(t->ctx, SST_E_ARG, std::string(who) + ": max_combos outside [" + std::to_string(least_combos) +
+                                       ", sst_final_max_combos()]");
   if (a->n_spec == 0) return SST_OK;
   // (frag_use may be NULL: every fragment is used)
   if (!a->seq_len || !a->pos_off || !a->skeleton || !a->alpha || !a->frag_off || !a->frag_code || !a->frag_su ||
@@ -3744,6 +3747,38 @@ extern "C" int sst_final_robust_device(sst_table* t, const sst_final_robust_args
   if (int e = set_device(c)) return e;
   Prof p(c, SST_K_FINAL_ROBUST);
   HIP_OK(c, sst::launch_final_robust(*a, t->args.w, t->n_rows, 3 * c->n_cu, c->stream));
+  return SST_OK;
+}
+
+extern "C" uint32_t sst_final_search_max_width(void) { return SST_FINAL_SEARCH_MAX_WIDTH; }
+
+extern "C" int sst_final_search_device(sst_table* t, const sst_final_search_args* a) {
+  if (!t) return SST_E_ARG;
+  if (!a) return fail(t->ctx, SST_E_ARG, std::string(__func__) + ": a NULL sst_final_search_args");
+  if (int e = final_check(t, &a->robust.base, __func__, 0)) return e;
+  if (a->max_width == 0 || a->max_width > SST_FINAL_SEARCH_MAX_WIDTH)
+    return fail(t->ctx, SST_E_ARG, std::string(__func__) + ": max_width outside [1, sst_final_search_max_width()]");
+  if (a->horizon > (1ull << 62)) return fail(t->ctx, SST_E_ARG, std::string(__func__) + ": horizon above 2^62");
+  const int64_t n_spec = a->robust.base.n_spec;
+  if (n_spec == 0) return SST_OK;
+  if (!a->robust.n_optional || !a->robust.cstar || !a->robust.rbest || !a->robust.rn_opt || !a->robust.rgap ||
+      !a->mode || !a->rounds || !a->nodes)
+    return fail(t->ctx, SST_E_ARG, std::string(__func__) + ": a NULL member of sst_final_search_args");
+  sst_ctx* c = t->ctx;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  if (int e = set_device(c)) return e;
+  // the workspace: the list (its length, then the spectra), then one slice per search workgroup
+  const int n_wg = (int)(n_spec < 2 * (int64_t)c->n_cu ? n_spec : 2 * (int64_t)c->n_cu);  // two per CU: the LDS
+  const uint64_t list_words = ((uint64_t)n_spec + 1 + 3) & ~3ull;
+  if (!c->final_search.ensure((list_words + (uint64_t)n_wg * sst::final_search_ws_words(a->max_width)) * 4))
+    return fail(c, SST_E_NOMEM, "device allocation failed (final search workspace)");
+  uint32_t* list = (uint32_t*)c->final_search.p;
+  {
+    Prof p(c, SST_K_FINAL_ROBUST);
+    HIP_OK(c, sst::launch_final_robust(a->robust, t->args.w, t->n_rows, 3 * c->n_cu, c->stream));
+  }
+  Prof p(c, SST_K_FINAL_SEARCH);
+  HIP_OK(c, sst::launch_final_search(*a, t->args.w, t->n_rows, list, list + list_words, n_wg, c->stream));
   return SST_OK;
 }
 

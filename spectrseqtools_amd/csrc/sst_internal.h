@@ -714,6 +714,11 @@ hipError_t launch_align(bool split, const sst_align_args& a, const sst_align_cap
 hipError_t launch_final(const sst_final_args& a, const int* w, int n_rows, int n_wg, hipStream_t st);
 // the robust final program (k_final_robust, sst_final.hip): the same body with the second, capped enumeration
 hipError_t launch_final_robust(const sst_final_robust_args& r, const int* w, int n_rows, int n_wg, hipStream_t st);
+// the bounded search (k_final_search_list, k_final_search; sst_final.hip) after launch_final_robust on the same
+// stream: list [1 + n_spec] words, ws n_wg slices of final_search_ws_words(max_width) words, n_wg workgroups
+uint64_t final_search_ws_words(uint32_t max_width);
+hipError_t launch_final_search(const sst_final_search_args& x, const int* w, int n_rows, uint32_t* list, uint32_t* ws,
+                               int n_wg, hipStream_t st);
 hipError_t launch_skel_alpha(int64_t n_spec, const int32_t* max_len, const uint64_t* skel_off, const uint64_t* skel,
                              const uint64_t* alpha, uint64_t canon0, uint64_t canon1, uint64_t* out, hipStream_t st);
 hipError_t launch_result_refs(const int8_t* status, int64_t n, const uint4* hits, uint64_t n_hits,

@@ -51,6 +51,12 @@ STATUS_NAMES = {FINAL_NONE: "NONE", FINAL_SOLVED: "SOLVED", FINAL_TOO_LARGE: "TO
                 FINAL_UNDECIDED: "UNDECIDED"}
 FINAL_SOLVE, FINAL_TAKE = 0, 1
 _HOST_BLOCK = 1 << 22               # elements of a block of interval sums (final_host)
+SEARCH_MAX_WIDTH = 1 << 16          # sst_final_search_max_width()
+SEARCH_DEFAULT_WIDTH = 1 << 12
+SEARCH_MAX_HORIZON = 1 << 62
+SEARCH_DEFAULT_HORIZON = 1 << 17    # two precision units: above every need of final_decisions / robust_decisions
+SEARCH_MAX_FREE = 48                # free positions of a searched spectrum
+SEARCH_ENUMERATED, SEARCH_SEARCHED = 1, 2   # SearchOutcome.mode (0: not SOLVED)
 
 
 @dataclass
@@ -182,6 +188,56 @@ class RobustOutcome:
                    rn_opt=np.zeros(S, np.uint32), rgap=np.full(S, NO_GAP, np.uint64))
 
 
+@dataclass
+class SearchOutcome:
+    """The bounded search's three further results per spectrum, parallel to a
+    FinalOutcome (include/sst.h, sst_final_search_device), as host arrays."""
+    mode: np.ndarray    # u8 0 not SOLVED, SEARCH_ENUMERATED, SEARCH_SEARCHED
+    rounds: np.ndarray  # u32 sweeps run in both passes (0 unless searched)
+    nodes: np.ndarray   # u64 nodes kept over all sweeps (0 unless searched)
+    horizon: int        # H: gap and rgap of a searched spectrum are min(true gap, H + 1)
+    widest: np.ndarray = None  # u32 the widest level of any sweep: the host model's only (None from the device)
+
+    _DTYPES = {"mode": np.uint8, "rounds": np.uint32, "nodes": np.uint64}
+
+    def __post_init__(self):
+        for k, dt in self._DTYPES.items():
+            setattr(self, k, np.ascontiguousarray(getattr(self, k), dtype=dt))
+        self.horizon = int(self.horizon)
+        if any(len(getattr(self, k)) != len(self.mode) for k in self._DTYPES):
+            raise ValueError("SearchOutcome: arrays of different lengths")
+
+    def __len__(self):
+        return len(self.mode)
+
+    def equals(self, other):
+        return self.horizon == other.horizon and \
+            all(np.array_equal(getattr(self, k), getattr(other, k)) for k in self._DTYPES)
+
+    def take(self, idx):
+        """The result of spectra idx, in that order (as FinalOutcome.take)."""
+        idx = np.asarray(idx, dtype=np.int64)
+        return SearchOutcome(horizon=self.horizon, widest=None if self.widest is None else self.widest[idx],
+                             **{k: getattr(self, k)[idx] for k in self._DTYPES})
+
+    @classmethod
+    def concat(cls, outcomes):
+        """Several results' spectra one after the other (as FinalOutcome.concat); one horizon."""
+        outcomes = list(outcomes)
+        if not outcomes or len({o.horizon for o in outcomes}) != 1:
+            raise ValueError("SearchOutcome.concat: nothing to concatenate, or different horizons")
+        widest = None if any(o.widest is None for o in outcomes) else np.concatenate([o.widest for o in outcomes])
+        return cls(horizon=outcomes[0].horizon, widest=widest,
+                   **{k: np.concatenate([getattr(o, k) for o in outcomes]) for k in cls._DTYPES})
+
+    @classmethod
+    def blank(cls, outcome, horizon):
+        """The outputs of spectra that are not SOLVED, one per spectrum of `outcome`."""
+        S = len(outcome)
+        return cls(mode=np.zeros(S, np.uint8), rounds=np.zeros(S, np.uint32), nodes=np.zeros(S, np.uint64),
+                   horizon=horizon, widest=np.zeros(S, np.uint32))
+
+
 def final_use(al, optional=False):
     """(use, undecided) from a keep-mode AlignOutcome: use u8 per fragment, 1
     for the LP_KEEP fragments (filter_with_lp, run to optimality, keeps exactly
@@ -232,11 +288,20 @@ def sequence_names(fo, outcome, g):
     return [outcome.row_names[int(r)] for r in fo.seq[int(fo.pos_off[g]):int(fo.pos_off[g + 1])]]
 
 
-def _check_max_combos(max_combos, who):
+def _check_max_combos(max_combos, who, least=1):
     max_combos = int(max_combos)
-    if not 1 <= max_combos <= FINAL_MAX_COMBOS:
-        raise ValueError(f"{who}: max_combos outside [1, 2^22]")
+    if not least <= max_combos <= FINAL_MAX_COMBOS:
+        raise ValueError(f"{who}: max_combos outside [{least}, 2^22]")
     return max_combos
+
+
+def _check_search(horizon, max_width, who):
+    horizon, max_width = int(horizon), int(max_width)
+    if not 0 <= horizon <= SEARCH_MAX_HORIZON:
+        raise ValueError(f"{who}: horizon outside [0, 2^62]")
+    if not 1 <= max_width <= SEARCH_MAX_WIDTH:
+        raise ValueError(f"{who}: max_width outside [1, 2^16]")
+    return horizon, max_width
 
 
 def _per_fragment(use, nf, who):
@@ -345,14 +410,37 @@ def _solve_spectrum(L, sets, row_mass, row_mod, mod_cap, cls, qfix, mn, mx, in_o
                 first = int(idx[at[0]])
     if n_feas == 0:
         return 0, 0, 0, NO_GAP, None, None, None
-    P, _ = prefix_of(np.array([first], dtype=np.int64))
     seq = np.array([sets[p][int(d)] for p, d in enumerate(digits_of([first])[0])], dtype=np.uint8)
-    pairs = P[:, ib] - P[:, ia] if len(internal) else None
+    iv, sm = _intervals_under(L, seq, row_mass, cls, q, mn, mx)
+    return n_feas, best, min(n_opt, 0xFFFFFFFF), (NO_GAP if nxt is None else nxt - best), seq, iv, sm
+
+
+def _interval_sums(P, Q, L, c, mn, mx, pairs):
+    """The sums of a fragment's admissible intervals in (l, r) order, the empty
+    one last, as differences of prefix sums: P(r + 1) - Q(l) ([n, n_iv]; P is Q
+    for the sums of one y).  c, mn, mx: its class and ends; pairs: (ia, ib) of
+    np.triu_indices(L + 1, k=1), read by an internal fragment."""
+    if c == 3:
+        return P[:, L:L + 1] - Q[:, 0:1]
+    if c == 1:
+        lo, hi = _ends(1, mn, mx)
+        return P[:, lo + 1:hi + 2] - Q[:, 0:1]
+    if c == 2:
+        lo, hi = _ends(2, mn, mx)
+        return P[:, L:L + 1] - Q[:, lo:hi + 1]
+    return np.concatenate([P[:, pairs[1]] - Q[:, pairs[0]], np.zeros((len(P), 1), np.int64)], axis=1)
+
+
+def _intervals_under(L, seq, row_mass, cls, q, mn, mx):
+    """(iv, sum) per fragment under the assignment seq (one row per position):
+    the first minimiser of c_j in (l, r) order, the empty interval last."""
+    P = np.concatenate([[0], np.cumsum([int(row_mass[r]) for r in seq], dtype=np.int64)]).astype(np.int64)[None, :]
+    ia, ib = np.triu_indices(L + 1, k=1)
     iv = np.empty(len(cls), np.uint16)
     sm = np.empty(len(cls), np.uint32)
     for j in range(len(cls)):
-        c, s = costs(P, j, pairs)
-        at = int(np.argmin(c[0]))  # the first minimiser: the smallest (l, r), the empty interval last
+        s = _interval_sums(P, P, L, int(cls[j]), int(mn[j]), int(mx[j]), (ia, ib))
+        at = int(np.argmin(np.abs(q[j] - FIX * s[0])))
         sm[j] = int(s[0, at])
         if cls[j] == 3:
             iv[j] = L - 1 if L else EMPTY_INTERVAL
@@ -362,7 +450,127 @@ def _solve_spectrum(L, sets, row_mass, row_mod, mod_cap, cls, qfix, mn, mx, in_o
             iv[j] = (_ends(2, int(mn[j]), int(mx[j]))[0] + at) << 8 | (L - 1)
         else:
             iv[j] = EMPTY_INTERVAL if at == len(ia) else int(ia[at]) << 8 | (int(ib[at]) - 1)
-    return n_feas, best, min(n_opt, 0xFFFFFFFF), (NO_GAP if nxt is None else nxt - best), seq, iv, sm
+    return iv, sm
+
+
+class _Search:
+    """The bounded search of one modelled, row-free spectrum by the definition
+    (include/sst.h, sst_final_search_device): nodes as arrays per level, the
+    bound over every admissible interval, Python / numpy integers."""
+
+    def __init__(self, L, sets, row_mass, row_mod, mod_cap, cls, qfix, mn, mx, optional, max_width):
+        self.L, self.cls, self.q, self.mn, self.mx = L, cls, qfix.astype(np.int64), mn, mx
+        self.optional, self.max_width, self.mod_cap = optional, max_width, mod_cap
+        self.free = [p for p in range(L) if len(sets[p]) > 1]
+        self.rows = [np.array(sets[p], dtype=np.int64) for p in self.free]
+        self.mass = np.array([int(m) for m in row_mass], dtype=np.int64)
+        self.is_mod = np.array([int(m != 0) for m in row_mod], dtype=np.int64)
+        one = [sets[p][0] for p in range(L)]
+        self.fixed_mod = sum(int(self.is_mod[one[p]]) for p in range(L) if len(sets[p]) == 1)
+        # per position the smallest and largest mass over A_i (an open position), and the one row's
+        self.wmin = np.array([min(int(self.mass[r]) for r in sets[p]) for p in range(L)], dtype=np.int64)
+        self.wmax = np.array([max(int(self.mass[r]) for r in sets[p]) for p in range(L)], dtype=np.int64)
+        all_mod = [int(all(self.is_mod[r] for r in rows)) for rows in self.rows]
+        self.all_mod_from = np.concatenate([np.cumsum(all_mod[::-1])[::-1], [0]]).astype(np.int64)
+        self.pairs = np.triu_indices(L + 1, k=1)
+        self.rounds = self.nodes = self.widest = 0
+
+    def n_feas(self):
+        """The feasible y, counted over the number of modified rows per free position."""
+        ways = {0: 1}  # modified rows among the free positions so far -> assignments
+        for rows in self.rows:
+            m = int(self.is_mod[rows].sum())
+            nxt = {}
+            for k, v in ways.items():
+                for add, mult in ((0, len(rows) - m), (1, m)):
+                    if mult and self.fixed_mod + k + add <= self.mod_cap:
+                        nxt[k + add] = nxt.get(k + add, 0) + v * mult
+            ways = nxt
+        return sum(ways.values()) if self.fixed_mod <= self.mod_cap else 0
+
+    def bound(self, fixed, cap=None):
+        """lb of the nodes `fixed` ([m, d] rows at the first d free positions):
+        the required fragments' lb_j summed, and with cap (c*_j per fragment) the
+        optional ones' min(lb_j, c*_j) too."""
+        m, d = fixed.shape
+        wmin, wmax = np.tile(self.wmin, (m, 1)), np.tile(self.wmax, (m, 1))
+        for k in range(d):
+            wmin[:, self.free[k]] = wmax[:, self.free[k]] = self.mass[fixed[:, k]]
+        zero = np.zeros((m, 1), np.int64)
+        Pmin = np.concatenate([zero, np.cumsum(wmin, axis=1)], axis=1)
+        Pmax = np.concatenate([zero, np.cumsum(wmax, axis=1)], axis=1)
+        lb = np.zeros(m, np.int64)
+        for j in range(len(self.cls)):
+            if self.optional[j] and cap is None:
+                continue
+            at = (int(self.cls[j]), int(self.mn[j]), int(self.mx[j]), self.pairs)
+            smin = _interval_sums(Pmin, Pmin, self.L, *at)
+            smax = _interval_sums(Pmax, Pmax, self.L, *at)
+            dist = np.maximum(0, np.maximum(FIX * smin - self.q[j], self.q[j] - FIX * smax)).min(axis=1)
+            lb += np.minimum(dist, cap[j]) if self.optional[j] else dist
+        return lb
+
+    def sweep(self, T, cap=None):
+        """Sweep(T): (leaves [m, n] as rows, their objectives), or None on overflow."""
+        T = min(int(T), (1 << 63) - 1)
+        self.rounds += 1
+        fixed, mods = np.zeros((1, 0), np.int64), np.array([self.fixed_mod], np.int64)
+        for d, rows in enumerate(self.rows):
+            m = len(fixed)
+            fixed = np.concatenate([np.repeat(fixed, len(rows), axis=0), np.tile(rows, m)[:, None]], axis=1)
+            mods = np.repeat(mods, len(rows)) + np.tile(self.is_mod[rows], m)
+            live = mods + self.all_mod_from[d + 1] <= self.mod_cap
+            fixed, mods = fixed[live], mods[live]
+            keep = np.zeros(len(fixed), bool)
+            for at in range(0, len(fixed), 4096):
+                keep[at:at + 4096] = self.bound(fixed[at:at + 4096], cap) <= T
+            fixed, mods = fixed[keep], mods[keep]
+            if len(fixed) > self.max_width:
+                return None
+            self.nodes += len(fixed)
+            self.widest = max(self.widest, len(fixed))
+        return fixed, self.bound(fixed, cap)
+
+    @staticmethod
+    def summary(obj, H):
+        """(min, how many leaves attain it, the smallest value in (min, min + H] minus it, else H + 1)"""
+        lo = int(obj.min())
+        above = obj[(obj > lo) & (obj <= min(lo + H, (1 << 63) - 1))]
+        return lo, min(int((obj == lo).sum()), 0xFFFFFFFF), (int(above.min()) - lo if len(above) else H + 1)
+
+
+def _search_spectrum(L, sets, row_mass, row_mod, mod_cap, cls, qfix, mn, mx, optional, H, max_width):
+    """The bounded search of one spectrum: None where a sweep overflows, else
+    (best, n_opt, gap, seq, iv, sum, cstar, rbest, rn_opt, rgap, rounds, nodes, widest)."""
+    s = _Search(L, sets, row_mass, row_mod, mod_cap, cls, qfix, mn, mx, optional, max_width)
+    T = max(H, FIX)
+    while True:
+        got = s.sweep(T)
+        if got is None:
+            return None
+        if len(got[0]):
+            break
+        T = min(4 * T, (1 << 63) - 1)
+    b = int(got[1].min())
+    if b + H > T:
+        got = s.sweep(b + H)
+        if got is None:
+            return None
+    leaves, obj = got
+    best, n_opt, gap = s.summary(obj, H)
+    first = min(tuple(int(r) for r in y) for y in leaves[obj == best])
+    seq = np.array([sets[p][0] for p in range(L)], dtype=np.uint8)
+    seq[s.free] = first
+    iv, sm = _intervals_under(L, seq, row_mass, cls, s.q, mn, mx)
+    cstar, rbest, rn_opt, rgap = 0, best, n_opt, gap
+    if optional.any():
+        c_star = np.where(optional, np.abs(s.q - FIX * sm.astype(np.int64)), np.iinfo(np.int64).max)
+        cstar = int(c_star[optional].sum())
+        got = s.sweep(best + cstar + H, cap=c_star)
+        if got is None:
+            return None
+        rbest, rn_opt, rgap = s.summary(got[1], H)
+    return best, n_opt, gap, seq, iv, sm, cstar, rbest, rn_opt, rgap, s.rounds, s.nodes, s.widest
 
 
 def final_host(outcome, precision, caps, row_cap, use=None, max_combos=FINAL_DEFAULT_COMBOS, undecided=None):
@@ -387,9 +595,25 @@ def final_robust_host(outcome, precision, caps, row_cap, use=None, max_combos=FI
     return _final_host(outcome, precision, caps, row_cap, use, max_combos, None, "final_robust_host")
 
 
-def _final_host(outcome, precision, caps, row_cap, use, max_combos, undecided, who):
-    """final_host (use in {0, 1}) and final_robust_host (use in {0, 1, 2}): (FinalOutcome, RobustOutcome)."""
-    max_combos = _check_max_combos(max_combos, who)
+def final_search_host(outcome, precision, caps, row_cap, use=None, max_combos=FINAL_DEFAULT_COMBOS,
+                      horizon=SEARCH_DEFAULT_HORIZON, max_width=SEARCH_DEFAULT_WIDTH):
+    """The robust final program with the bounded search, by the definition
+    (include/sst.h, sst_final_search_device): (FinalOutcome, RobustOutcome,
+    SearchOutcome).  A spectrum within max_combos is enumerated as
+    final_robust_host does (mode 1); a larger one (max_combos may be 0: every
+    one) is searched level by level over its free positions, keeping the nodes
+    whose lower bound is within the threshold (mode 2 where SOLVED): its gap
+    and rgap are min(true gap, horizon + 1).  The other arguments as
+    final_robust_host's."""
+    use = _per_fragment_robust(use, int(outcome.frag_off[-1]), "final_search_host")
+    search = _check_search(horizon, max_width, "final_search_host")
+    return _final_host(outcome, precision, caps, row_cap, use, max_combos, None, "final_search_host", search)
+
+
+def _final_host(outcome, precision, caps, row_cap, use, max_combos, undecided, who, search=None):
+    """final_host (use in {0, 1}) and final_robust_host (use in {0, 1, 2}): (FinalOutcome, RobustOutcome);
+    final_search_host (search = (horizon, max_width)): and a SearchOutcome."""
+    max_combos = _check_max_combos(max_combos, who, 0 if search else 1)
     S = len(outcome)
     n_rows = len(outcome.row_mass)
     row_mod = np.ascontiguousarray(caps[0], dtype=np.uint8)
@@ -405,6 +629,7 @@ def _final_host(outcome, precision, caps, row_cap, use, max_combos, undecided, w
     undecided = _per_spectrum(undecided, S, who)
     fo = FinalOutcome.blank(outcome)
     ro = RobustOutcome.blank(outcome)
+    so = SearchOutcome.blank(outcome, search[0]) if search else None
     with np.errstate(all="ignore"):
         u = np.asarray(outcome.frag_su, dtype=np.float64) / np.float64(precision)
         in_model = np.abs(u) < 2.0 ** 32  # (False for NaN and the infinities)
@@ -444,11 +669,14 @@ def _final_host(outcome, precision, caps, row_cap, use, max_combos, undecided, w
                    for r in _rows_of(int(outcome.alpha[g][0]), int(outcome.alpha[g][1]), n_rows)):
             fo.status[g] = FINAL_NOT_FREE
             continue
+        optional = use[on] == 2
+        solve = (L, sets, outcome.row_mass, row_mod, cap, cls, qfix[on], mn, mx)
+        if combos > max_combos and search:
+            fo.status[g] = _search_into(fo, ro, so, g, p, on, solve, optional, *search)
+            continue
         if combos > max_combos:
             fo.status[g] = FINAL_TOO_LARGE
             continue
-        optional = use[on] == 2
-        solve = (L, sets, outcome.row_mass, row_mod, cap, cls, qfix[on], mn, mx)
         n_feas, best, n_opt, gap, seq, iv, sm = _solve_spectrum(*solve, in_obj=~optional if optional.any() else None)
         if n_feas == 0:
             fo.status[g] = FINAL_INFEASIBLE
@@ -460,7 +688,29 @@ def _final_host(outcome, precision, caps, row_cap, use, max_combos, undecided, w
             c_star = np.where(optional, np.abs(qfix[on] - FIX * sm.astype(np.int64)), np.iinfo(np.int64).max)
             ro.n_optional[g], ro.cstar[g] = int(optional.sum()), int(c_star[optional].sum())
             _, ro.rbest[g], ro.rn_opt[g], ro.rgap[g], _, _, _ = _solve_spectrum(*solve, cap=c_star)
-    return fo, ro
+        if search:
+            so.mode[g] = SEARCH_ENUMERATED
+    return (fo, ro, so) if search else (fo, ro)
+
+
+def _search_into(fo, ro, so, g, p, on, solve, optional, H, max_width):
+    """The searched spectrum g: its status, and where that is SOLVED its outputs written."""
+    sets = solve[1]
+    if sum(len(rows) > 1 for rows in sets) > SEARCH_MAX_FREE:
+        return FINAL_TOO_LARGE
+    s = _Search(*solve, optional, max_width)
+    n_feas = s.n_feas()
+    if n_feas == 0:
+        return FINAL_INFEASIBLE
+    got = _search_spectrum(*solve, optional, H, max_width)
+    if got is None:
+        return FINAL_TOO_LARGE
+    best, n_opt, gap, seq, iv, sm, cstar, rbest, rn_opt, rgap, rounds, nodes, widest = got
+    fo.n_feas[g], fo.best[g], fo.n_opt[g], fo.gap[g] = min(n_feas, (1 << 64) - 1), best, n_opt, gap
+    fo.seq[p], fo.iv[on], fo.sum[on] = seq, iv, sm
+    ro.n_optional[g], ro.cstar[g], ro.rbest[g], ro.rn_opt[g], ro.rgap[g] = int(optional.sum()), cstar, rbest, rn_opt, rgap
+    so.mode[g], so.rounds[g], so.nodes[g], so.widest[g] = SEARCH_SEARCHED, rounds, nodes, widest
+    return FINAL_SOLVED
 
 
 def final_device(dp_table, outcome, use=None, max_combos=FINAL_DEFAULT_COMBOS, undecided=None, caps=None, row_cap=None):
@@ -505,9 +755,9 @@ def final_robust_device(dp_table, outcome, use=None, max_combos=FINAL_DEFAULT_CO
     return _one_stream(_final_device)(dp_table, outcome, use, row_mod, mod_cap, row_cap, max_combos, robust=True)
 
 
-def _device_inputs(dp_table, outcome, max_combos, caps, row_cap, who):
+def _device_inputs(dp_table, outcome, max_combos, caps, row_cap, who, least=1):
     """(max_combos, row_mod, mod_cap, row_cap) of a device call, checked against the table and the outcome."""
-    max_combos = _check_max_combos(max_combos, who)
+    max_combos = _check_max_combos(max_combos, who, least)
     masses = [int(m.mass) for m in dp_table.masses]
     if masses != [int(x) for x in outcome.row_mass]:
         raise ValueError(f"{who}: the outcome is not on this table's rows")
@@ -523,9 +773,26 @@ def _device_inputs(dp_table, outcome, max_combos, caps, row_cap, who):
     return max_combos, row_mod, mod_cap, row_cap
 
 
-def _final_device(dp_table, o, use, row_mod, mod_cap, row_cap, max_combos, robust=False):
+def final_search_device(dp_table, outcome, use=None, max_combos=FINAL_DEFAULT_COMBOS, horizon=SEARCH_DEFAULT_HORIZON,
+                        max_width=SEARCH_DEFAULT_WIDTH, caps=None, row_cap=None):
+    """The robust final program with the bounded search on dp_table's device
+    (sst_final_search_device): (FinalOutcome, RobustOutcome, SearchOutcome), with
+    the upload / launch / download shape of final_device.  The arguments as
+    final_search_host's; caps, row_cap: as final_device's."""
+    from .pipeline_device import _one_stream
+
+    search = _check_search(horizon, max_width, "final_search_device")
+    max_combos, row_mod, mod_cap, row_cap = _device_inputs(dp_table, outcome, max_combos, caps, row_cap,
+                                                           "final_search_device", least=0)
+    use = _per_fragment_robust(use, int(outcome.frag_off[-1]), "final_search_device")
+    return _one_stream(_final_device)(dp_table, outcome, use, row_mod, mod_cap, row_cap, max_combos, robust=True,
+                                      search=search)
+
+
+def _final_device(dp_table, o, use, row_mod, mod_cap, row_cap, max_combos, robust=False, search=None):
     """One launch of sst_final_program_device (a FinalOutcome), or with robust of
-    sst_final_robust_device (a FinalOutcome and a RobustOutcome)."""
+    sst_final_robust_device (a FinalOutcome and a RobustOutcome), or with search
+    = (horizon, max_width) of sst_final_search_device (and a SearchOutcome)."""
     import torch
 
     dt = dp_table.device_table
@@ -533,7 +800,8 @@ def _final_device(dp_table, o, use, row_mod, mod_cap, row_cap, max_combos, robus
     dev = torch.device("cuda", eng.device)
     S, nf, n_pos = len(o), int(o.frag_off[-1]), int(o.pos_off[-1])
     if S == 0:
-        return (FinalOutcome.blank(o), RobustOutcome.blank(o)) if robust else FinalOutcome.blank(o)
+        blank = (FinalOutcome.blank(o), RobustOutcome.blank(o)) if robust else FinalOutcome.blank(o)
+        return blank + (SearchOutcome(np.zeros(0), np.zeros(0), np.zeros(0), search[0]),) if search else blank
 
     def up(x, dtype, n=1):  # (never an empty allocation: the entry point refuses NULL)
         x = np.ascontiguousarray(x, dtype=dtype).reshape(-1)
@@ -550,7 +818,9 @@ def _final_device(dp_table, o, use, row_mod, mod_cap, row_cap, max_combos, robus
             out(S, torch.int64), out(n_pos, torch.uint8), out(nf, torch.int16), out(nf, torch.int32)]
     r_outs = [out(S, torch.int32), out(S, torch.int64), out(S, torch.int64), out(S, torch.int32),
               out(S, torch.int64)] if robust else []
-    args = _native.FinalRobustArgs() if robust else _native.FinalArgs()
+    s_outs = [out(S, torch.uint8), out(S, torch.int32), out(S, torch.int64)] if search else []
+    top = _native.FinalSearchArgs() if search else None
+    args = top.robust if search else _native.FinalRobustArgs() if robust else _native.FinalArgs()
     a = args.base if robust else args
     a.n_spec = S
     (a.seq_len, a.pos_off, a.skeleton, a.alpha, a.frag_off, a.frag_code, a.frag_su, a.frag_min_end, a.frag_max_end,
@@ -561,9 +831,12 @@ def _final_device(dp_table, o, use, row_mod, mod_cap, row_cap, max_combos, robus
     a.status, a.combos, a.n_feas, a.best, a.n_opt, a.gap, a.seq, a.iv, a.sum = (x.data_ptr() for x in outs)
     if robust:
         args.n_optional, args.cstar, args.rbest, args.rn_opt, args.rgap = (x.data_ptr() for x in r_outs)
-    name = "sst_final_robust_device" if robust else "sst_final_program_device"
+    if search:
+        top.horizon, top.max_width = search
+        top.mode, top.rounds, top.nodes = (x.data_ptr() for x in s_outs)
+    name = "sst_final_search_device" if search else "sst_final_robust_device" if robust else "sst_final_program_device"
     torch.cuda.synchronize(dev)
-    eng.check(getattr(eng._lib, name)(dt.handle, ctypes.byref(args)), name)
+    eng.check(getattr(eng._lib, name)(dt.handle, ctypes.byref(top if search else args)), name)
     eng.synchronize()
     status, combos, n_feas, best, n_opt, gap, seq, iv, sm = (x.cpu().numpy() for x in outs)
     fo = FinalOutcome(frag_off=np.array(o.frag_off, dtype=np.int64), pos_off=np.array(o.pos_off, dtype=np.int64),
@@ -573,5 +846,10 @@ def _final_device(dp_table, o, use, row_mod, mod_cap, row_cap, max_combos, robus
     if not robust:
         return fo
     n_optional, cstar, rbest, rn_opt, rgap = (x.cpu().numpy()[:S] for x in r_outs)
-    return fo, RobustOutcome(n_optional=n_optional.view(np.uint32), cstar=cstar.view(np.uint64),
-                             rbest=rbest.view(np.uint64), rn_opt=rn_opt.view(np.uint32), rgap=rgap.view(np.uint64))
+    ro = RobustOutcome(n_optional=n_optional.view(np.uint32), cstar=cstar.view(np.uint64),
+                       rbest=rbest.view(np.uint64), rn_opt=rn_opt.view(np.uint32), rgap=rgap.view(np.uint64))
+    if not search:
+        return fo, ro
+    mode, rounds, nodes = (x.cpu().numpy()[:S] for x in s_outs)
+    return fo, ro, SearchOutcome(mode=mode, rounds=rounds.view(np.uint32), nodes=nodes.view(np.uint64),
+                                 horizon=search[0])

@@ -1730,7 +1730,8 @@ def mirror_outcome(dp_table, obs, su_mass, seq_mass, max_len, breakage_dict, int
 def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=None, intensity=None,
               intensity_cutoff=0.5e6, mass_cutoff=50000, limits=DeviceLimits(), fallback="mirror", name_hash=None,
               trim=True, explanation_masses=None, record=None, align=False, align_split=False, align_caps=False,
-              align_keep=False, align_final=False, final_max_combos=None, align_robust=False):
+              align_keep=False, align_final=False, final_max_combos=None, align_robust=False, align_search=False,
+              search_horizon=None, search_width=None):
     """These spectra -> what Predictor.predict holds when it reaches its MILP
     stages (prediction.py:63-103), as a BatchOutcome: the six device stages
     (classify_device, fixpoint_device, bins_device, skeleton_device,
@@ -1793,7 +1794,14 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
     optional, no spectrum is FINAL_UNDECIDED); returns (BatchOutcome,
     AlignOutcome, FinalOutcome, RobustOutcome).  Spectra the device ran take
     final_robust_device, mirror-routed ones final_robust_host
-    (final_program.robust_decisions reads the pair)."""
+    (final_program.robust_decisions reads the pair).
+    align_search=True implies what align_robust implies and runs the robust
+    final program with the bounded search in its place: a spectrum above
+    final_max_combos (0 is allowed here: every one) is searched, not given up
+    (final_program.final_search_host; search_horizon, search_width: its horizon
+    and max_width, None: the defaults); returns (BatchOutcome, AlignOutcome,
+    FinalOutcome, RobustOutcome, SearchOutcome).  Spectra the device ran take
+    final_search_device, mirror-routed ones final_search_host."""
     from .masses import EXPLANATION_MASSES, TOLERANCE
     from .pipeline import max_len_of
 
@@ -1868,6 +1876,7 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
                                frag_max_end=h["max_end"], breakage_names=names, row_names=dev_out.row_names,
                                row_mass=dev_out.row_mass)
     m_idx = np.flatnonzero(reason)
+    align_robust = align_robust or align_search
     align_final = align_final or align_robust
     align_keep = align_keep or align_final
     align_split = align_split or align_final
@@ -1883,11 +1892,18 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
 
         combos = final_program.FINAL_DEFAULT_COMBOS if final_max_combos is None else final_max_combos
         use, undecided = final_program.final_use(dev_al, optional=align_robust)
-        if align_robust:
+        search = dict(horizon=final_program.SEARCH_DEFAULT_HORIZON if search_horizon is None else search_horizon,
+                      max_width=final_program.SEARCH_DEFAULT_WIDTH if search_width is None else search_width)
+        if align_search:
+            dev_fo, dev_ro, dev_so = final_program.final_search_device(dp_table, dev_out, use=use, max_combos=combos,
+                                                                       **search)
+        elif align_robust:
             dev_fo, dev_ro = final_program.final_robust_device(dp_table, dev_out, use=use, max_combos=combos)
         else:
             dev_fo = final_program.final_device(dp_table, dev_out, use=use, max_combos=combos, undecided=undecided)
     if not len(m_idx):
+        if align_search:
+            return dev_out, dev_al, dev_fo, dev_ro, dev_so
         if align_robust:
             return dev_out, dev_al, dev_fo, dev_ro
         return (dev_out, dev_al, dev_fo) if align_final else (dev_out, dev_al) if align else dev_out
@@ -1906,17 +1922,25 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
                 for o in mirrored]
         al = alignment.AlignOutcome.concat([dev_al] + m_al)
         if align_final:
-            m_fo, m_ro = [], []
+            m_fo, m_ro, m_so = [], [], []
             for o, a in zip(mirrored, m_al):
                 use, undecided = final_program.final_use(a, optional=align_robust)
                 host_args = (o, dp_table.precision, alignment.lp_caps(dp_table, o), alignment.lp_row_caps(dp_table, o))
-                if align_robust:
+                if align_search:
+                    f, r, so = final_program.final_search_host(*host_args, use=use, max_combos=combos, **search)
+                    m_ro.append(r)
+                    m_so.append(so)
+                elif align_robust:
                     f, r = final_program.final_robust_host(*host_args, use=use, max_combos=combos)
                     m_ro.append(r)
                 else:
                     f = final_program.final_host(*host_args, use=use, max_combos=combos, undecided=undecided)
                 m_fo.append(f)
             fo = final_program.FinalOutcome.concat([dev_fo] + m_fo).take(where)
+            if align_search:
+                return (both.take(where), al.take(where), fo,
+                        final_program.RobustOutcome.concat([dev_ro] + m_ro).take(where),
+                        final_program.SearchOutcome.concat([dev_so] + m_so).take(where))
             if align_robust:
                 return both.take(where), al.take(where), fo, final_program.RobustOutcome.concat([dev_ro] + m_ro).take(where)
             return both.take(where), al.take(where), fo

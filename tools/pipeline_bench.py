@@ -50,7 +50,7 @@ GPU-busy share of its wall time.
 
 Usage: python tools/pipeline_bench.py [--spectra 100000] [--seed 7] [--host-driven]
        [--backend nccl|gloo] [--dump-outcomes DIR] [--as-rank R] [--handoff [--handoff-repeats 3]]
-       [--align | --align-split] [--align-caps | --align-keep] [--align-final] [--align-robust] [--modification-rate 0.5]
+       [--align | --align-split] [--align-caps | --align-keep] [--align-final] [--align-robust | --align-search] [--modification-rate 0.5]
 """
 import argparse
 import json
@@ -388,8 +388,72 @@ def final_stage(dp, out, al, kernels, max_combos):
             "kernel_ms": {"k_final_program": kern.get("k_final_program", (0.0, 0))[0]}}
 
 
-def robust_stage(dp, out, al, kernels, max_combos):
-    """--align-robust: the robust final program (final_program.
+def free_positions(out):
+    """Free positions (|A_i| > 1) per spectrum of a BatchOutcome (i64)."""
+    spec = np.repeat(np.arange(len(out)), np.diff(out.pos_off))
+    skel = np.asarray(out.skeleton, dtype=np.uint64).reshape(-1, 2)
+    alpha = np.asarray(out.alpha, dtype=np.uint64).reshape(-1, 2)[spec]
+    sets = np.where((skel != 0).any(axis=1)[:, None], skel & alpha, alpha)
+    n_rows = len(out.row_mass)
+    sets[:, 0] &= np.uint64(((1 << min(n_rows, 64)) - 1) & ~1)  # rows below n_rows; row 0 is no row of a set
+    sets[:, 1] &= np.uint64((1 << min(max(0, n_rows - 64), 64)) - 1)
+    size = np.unpackbits(np.ascontiguousarray(sets).view(np.uint8), axis=1).sum(axis=1)
+    return np.bincount(spec, weights=size > 1, minlength=len(out)).astype(np.int64)
+
+
+def search_record(dp, out, use, fo, ro, so, max_combos, max_width, sample=64):
+    """--align-search: what the bounded search did.  The counts of enumerated
+    and searched spectra; among the searched SOLVED, TOO_LARGE by cause (more
+    than 48 free positions, or a level wider than max_width) and TAKE;
+    percentiles of rounds and nodes over the searched SOLVED ones, and of the
+    widest level over an evenly spaced sample of at most 64 of them (the host
+    model's at the run's max_width: the entry point has no output for it, and
+    the model's time grows with the nodes it keeps); whether every spectrum the robust program alone solves has
+    identical arrays."""
+    from spectrseqtools_amd import alignment
+    from spectrseqtools_amd import final_program as fp
+
+    live = ~np.isin(fo.status, (fp.FINAL_NONE, fp.FINAL_SKIPPED, fp.FINAL_NOT_FREE)) & (fo.combos > 0)
+    searched = live & (fo.combos > np.uint64(max_combos))
+    solved = searched & (fo.status == fp.FINAL_SOLVED)
+    too_large = searched & (fo.status == fp.FINAL_TOO_LARGE)
+    many_free = too_large & (free_positions(out) > fp.SEARCH_MAX_FREE)
+    dec = fp.robust_decisions(fo, ro)
+    pct = lambda x: {f"p{q}": float(np.percentile(x, q)) for q in (50, 90, 99, 100)} if len(x) else {}  # noqa: E731
+    at = np.flatnonzero(solved)
+    at = at[np.unique(np.linspace(0, len(at) - 1, min(sample, len(at))).astype(np.int64))] if len(at) else at
+    widest = np.zeros(0)
+    if len(at):
+        src, _ = pipeline_segments(out.frag_off, at)
+        sub = out.take(at)
+        host = fp.final_search_host(sub, dp.precision, alignment.lp_caps(dp, sub), alignment.lp_row_caps(dp, sub),
+                                    use=use[src], max_combos=max_combos, horizon=so.horizon, max_width=max_width)
+        widest = host[2].widest[host[2].mode == fp.SEARCH_SEARCHED]
+    r_fo, r_ro = fp.final_robust_device(dp, out, use=use, max_combos=max(1, max_combos))
+    was = np.flatnonzero(r_fo.status == fp.FINAL_SOLVED)
+    return {"horizon": int(so.horizon), "enumerated": int((so.mode == fp.SEARCH_ENUMERATED).sum()),
+            "searched": int(searched.sum()), "searched_solved": int(solved.sum()),
+            "searched_infeasible": int((searched & (fo.status == fp.FINAL_INFEASIBLE)).sum()),
+            "searched_too_large_free_positions": int(many_free.sum()),
+            "searched_too_large_width": int((too_large & ~many_free).sum()),
+            "searched_take": int(dec[solved].sum()), "rounds": pct(so.rounds[solved]), "nodes": pct(so.nodes[solved]),
+            "widest_level_sample": dict(pct(widest), spectra=int(len(widest))),
+            "robust_too_large": int((r_fo.status == fp.FINAL_TOO_LARGE).sum()),
+            "robust_solved": int(len(was)),
+            "robust_solved_identical": bool(fo.take(was).equals(r_fo.take(was)) and ro.take(was).equals(r_ro.take(was)))}
+
+
+def pipeline_segments(off, idx):
+    from spectrseqtools_amd.pipeline_device import _segments
+
+    return _segments(np.asarray(off, dtype=np.int64), np.asarray(idx, dtype=np.int64))
+
+
+def robust_stage(dp, out, al, kernels, max_combos, search=None):
+    """--align-search (search = (horizon, max_width)): the same stage through
+    final_program.final_search_device, with a "search" record (search_record)
+    and k_final_search's time.
+    --align-robust: the robust final program (final_program.
     final_robust_device) with the certificate's KEEP fragments required and its
     LP_SOLVE fragments optional, so that no spectrum is left out.  Its seconds
     run from the host arrays in to the host arrays out (uploads, k_final_robust,
@@ -404,9 +468,13 @@ def robust_stage(dp, out, al, kernels, max_combos):
     _, was_undecided = fp.final_use(al)
     kernels()
     t0 = time.perf_counter()
-    fo, ro = fp.final_robust_device(dp, out, use=use, max_combos=max_combos)
+    if search:
+        fo, ro, so = fp.final_search_device(dp, out, use=use, max_combos=max_combos, horizon=search[0], max_width=search[1])
+    else:
+        fo, ro = fp.final_robust_device(dp, out, use=use, max_combos=max_combos)
     s = time.perf_counter() - t0
     kern = kernels()
+    more = {"search": dict(search_record(dp, out, use, fo, ro, so, max_combos, int(search[1])), max_width=int(search[1]))} if search else {}
     live = np.diff(out.frag_off) > 0
     n_live = max(1, int(live.sum()))
     dec = fp.robust_decisions(fo, ro)
@@ -436,8 +504,10 @@ def robust_stage(dp, out, al, kernels, max_combos):
                                                                                    return_counts=True))},
                 "n_optional_max": int(n_opt_of.max(initial=0))},
             "assignments_enumerated": int(fo.combos[solved].sum() + fo.combos[solved & (ro.n_optional > 0)].sum()),
-            "path": "device (sst_final_robust_device), host arrays in and out", "kernels": kern,
-            "kernel_ms": {"k_final_robust": kern.get("k_final_robust", (0.0, 0))[0]}}
+            "path": f"device ({'sst_final_search_device' if search else 'sst_final_robust_device'}), host arrays in and out",
+            "kernels": kern,
+            "kernel_ms": {k: kern.get(k, (0.0, 0))[0] for k in ("k_final_robust",) + (("k_final_search",) if search else ())},
+            **more}
 
 
 def align_stage(pd, dp, rows, ln, post, kernels, split=False, caps=False, keep=False, hold=None):
@@ -620,14 +690,23 @@ def main():
                          "with its seconds, k_final_robust's time, the status and TAKE shares, and the formerly "
                          "undecided spectra's TAKE share, failed conditions and n_optional (n_optional_counts: 8 "
                          "stands for 8 and more)")
+    ap.add_argument("--align-search", action="store_true",
+                    help="--align-robust through the bounded search (final_program.final_search_device): spectra above "
+                         "--final-max-combos are searched, not given up.  The stage \"final_robust\" also carries "
+                         "\"search\": enumerated and searched spectra, the searched ones SOLVED, TOO_LARGE by cause and "
+                         "TAKE, percentiles of rounds, nodes and the widest level")
+    ap.add_argument("--search-horizon", type=int, default=1 << 17, help="--align-search: the horizon H")
+    ap.add_argument("--search-width", type=int, default=1 << 12, help="--align-search: max_width (up to 2^16)")
     ap.add_argument("--final-max-combos", type=int, default=1 << 20,
-                    help="--align-final, --align-robust: assignments enumerated per spectrum at most (up to 2^22)")
+                    help="--align-final, --align-robust: assignments enumerated per spectrum at most (up to 2^22; "
+                         "--align-search: 0 searches every spectrum)")
     ap.add_argument("--modification-rate", type=float, default=0.5,
                     help="the sequences' universal modification rate: the synthetic spectra's and the table's "
                          "SequenceInformation's (0.05: the low-modification-rate variant)")
     ap.add_argument("--as-rank", type=int, default=None,
                     help="single process: generate the spectra rank R of a multi-rank run would get")
     args = ap.parse_args()
+    args.align_robust = args.align_robust or args.align_search
     args.align_keep = args.align_keep or args.align_final or args.align_robust
     args.align_split = args.align_split or args.align_final or args.align_robust
     args.align_caps = args.align_caps or args.align_keep
@@ -731,7 +810,8 @@ def main():
             if args.align_final:
                 final_stage(dp, held["outcome"], held["certificate"], lambda: {}, args.final_max_combos)
             if args.align_robust:
-                robust_stage(dp, held["outcome"], held["certificate"], lambda: {}, args.final_max_combos)
+                robust_stage(dp, held["outcome"], held["certificate"], lambda: {}, args.final_max_combos,
+                             (args.search_horizon, args.search_width) if args.align_search else None)
         # the reach buffer at length_device's batch budget, as a serving
         # process holds it: the timed stage allocates nothing (its hipMalloc /
         # hipFree of tens of GB took 0.1-3 s from run to run)
@@ -913,7 +993,8 @@ def main():
             progress("final")
         if args.align_robust:
             barrier()
-            stages["final_robust"] = robust_stage(dp, held["outcome"], held["certificate"], kernels, args.final_max_combos)
+            stages["final_robust"] = robust_stage(dp, held["outcome"], held["certificate"], kernels, args.final_max_combos,
+                                                  (args.search_horizon, args.search_width) if args.align_search else None)
             stages["final_robust"]["s"] = tmax(stages["final_robust"]["s"])
             busy(stages["final_robust"])
             progress("final_robust")
