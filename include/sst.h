@@ -1445,6 +1445,127 @@ typedef struct sst_final_search_args {
 uint32_t sst_final_search_max_width(void);
 int sst_final_search_device(sst_table* t, const sst_final_search_args* a);
 
+/* The length program: the optimum of the program determine_lp_score builds, per
+ * candidate sequence length.  SkeletonBuilder.build_skeleton chooses the length
+ * with select_sequence_length_with_lp first (skeleton_building.py:198-289): for
+ * every c in [lower, upper] it combines the two skeletons at c, builds one
+ * LinearProgramInstance over the terminal fragments and reads only the optimal
+ * objective value (minimize_error, linear_program.py:227-236); the smallest
+ * value among the lengths validate_sequence_length_by_mass accepts wins, and a
+ * result below 1 hands the choice to the Jaccard selection (:44-57).  Here that
+ * value is enumerated, not solved.
+ * Per spectrum g (what build_skeleton holds at :45): M = max_len[g], the walk's
+ *   length; the START skeleton S_0 .. S_{M-1} and the REVERSED END skeleton
+ *   E_0 .. E_{M-1} (:41), two u64 over table rows each, at skeleton +
+ *   2 skel_off[g] and skeleton + 2 (skel_off[g] + M); the skeleton alphabet
+ *   alpha + 2 g; the terminal fragments frag_off[g] .. frag_off[g + 1]: the START
+ *   walk's kept rows, then the END walk's kept rows whose index no START row has
+ *   (:262-264; this does not depend on c), each with frag_code (side bits as
+ *   everywhere: START = bit 2, END = bit 3), su, and the walk's RAW min_end /
+ *   max_end.  Its candidates cand_off[g] .. cand_off[g + 1], each with its length
+ *   cand_len[k] = c (the caller lists lower .. upper, or nothing where the bounds
+ *   raised), valid[k] and mod_cap[k].
+ * Candidate c, n = max(c, 0) the number of positions of its program:
+ *   Combined skeleton (:494-516): position i takes S_i & E_{M-c+i} if that is
+ *     non-zero, else S_i | E_{M-c+i}.  A_i from it as sst_align_windows_device
+ *     defines the position sets (alpha where the position is empty, row 0
+ *     excluded).  mod_cap[k] = int(ceil(modification_rate * c)), row caps
+ *     row_cap[c * n_rows + r], row_mod: all as keep mode's inputs, computed by the
+ *     caller.  The row-free test is keep mode's, at length c.
+ *   Ends (:267-276, no clamping): a START row has mn = min_end - 1, mx =
+ *     max_end - 1; an END row mn = n - min_end, mx = n - max_end.
+ *   Shape: the contiguous runs of positions, the empty one included, that agree
+ *     with what _set_x leaves (linear_program.py:74-102; later fixings override
+ *     earlier ones, Python's negative indices wrap, an index outside [-n, n - 1]
+ *     raises and determine_lp_score returns inf, :279-286):
+ *       START and END ("START_END")  WHOLE, [0, n - 1]
+ *       START only  RAISES iff mn >= n or mx + 1 < -n.  Else, if mx + 1 <= 0:
+ *                   EMPTY (every x is 0; the empty interval only).  Else, if
+ *                   mn < 0: not modelled (no x is fixed to 1).  Else PREFIX
+ *                   [0, e], e in [min(mn, mx), min(mx, n - 1)].
+ *       END only    RAISES iff mx > n or mn < -n.  Else, if mn < 0: WHOLE (the
+ *                   wrapped range fixes every x to 1).  Else, if mn >= n: EMPTY
+ *                   if mx == n, otherwise not modelled.  Else SUFFIX [s, n - 1],
+ *                   s in [max(0, min(mx, mn)), mn].
+ *       neither     not modelled (no terminal fragment).
+ *     Inside [0, n - 1] this is sst_align_windows_device's rule.
+ *   Cost and objective: the final program's.  qfix_j = rint(su_j / prec *
+ *     65536) (ties to even; |su_j / prec| < 2^32, at most 16 384 fragments),
+ *     c_j(y) = min over the fragment's shape of |qfix_j - 65536 S_y(l, r)| (the
+ *     empty interval: |qfix_j|), obj(y) = the sum over ALL terminal fragments, y
+ *     feasible iff at most mod_cap[k] of its rows are modified; combos, n_feas as
+ *     there.
+ *   Status (u8), in precedence order:
+ *     SST_LEN_INVALID       valid[k] == 0: validate_sequence_length_by_mass
+ *                           (:291-313) rejects c, so c is never chosen and never
+ *                           updates best_val (:244-250).  Nothing is computed.
+ *                           valid is the caller's: the f64 sums in the
+ *                           reference's order.
+ *     SST_LEN_RAISES        some fragment raises: the value is exactly +inf
+ *     SST_LEN_NOT_MODELLED  c < 1, c > 253 or c > M (combine_skeleton_sequences
+ *                           raises there); no terminal fragment (what the solver
+ *                           layer returns for an empty objective is not pinned
+ *                           here); more than 16 384 fragments or one outside the
+ *                           fixed-point limits; a shape that is not modelled
+ *     SST_LEN_INFEASIBLE    an empty A_i, or n_feas == 0.  The reference reads
+ *                           objective.value() without looking at the solve
+ *                           status: the value is the solver's and is not claimed.
+ *     SST_LEN_NOT_FREE      not row-free: the per-row caps may bind
+ *     SST_LEN_TOO_LARGE     combos > max_combos (1 <= max_combos <=
+ *                           SST_FINAL_MAX_COMBOS)
+ *     SST_LEN_SOLVED        best = min obj over the feasible y
+ *   Outputs per candidate: status; combos (0 unless the status is INFEASIBLE,
+ *     NOT_FREE, TOO_LARGE or SOLVED; 0 for an empty A_i); n_feas and best (0
+ *     unless SOLVED).  Every element is written on every call.
+ * What SOLVED proves: as sst_final_program_device's "What SOLVED proves", points
+ * one to three -- in a row-free candidate the feasible y are the program's; for a
+ * fixed y the x_j are independent and take exactly the shape's intervals; best /
+ * 65536 * prec is within n_frag * 2^-16 * prec of the program's real optimum.  So
+ * two SOLVED candidates whose best differ by more than 2 n_frag units are ordered
+ * as their real optima are.  The claim is for solves run to optimality
+ * (timeLimit(short) may cut one off); no solver runs in this project: the claim
+ * is proven and held to a brute force.
+ * One kernel (k_length_program, sst_length_program.hip: one candidate per
+ * workgroup, lanes over the indices of y) on the ctx stream; device pointers; no
+ * scratch buffer beyond the outputs, no global atomics.  SST_E_ARG with a message
+ * for a NULL struct or, with n_spec > 0, a NULL member; n_spec or n_cand < 0;
+ * max_combos of 0 or above the limit; a non-positive or non-finite prec; and the
+ * row-mass limits of the align calls.  n_spec == 0 is SST_OK, and so is n_cand
+ * == 0 (nothing is written). */
+#define SST_LEN_INVALID 0
+#define SST_LEN_RAISES 1
+#define SST_LEN_NOT_MODELLED 2
+#define SST_LEN_INFEASIBLE 3
+#define SST_LEN_NOT_FREE 4
+#define SST_LEN_TOO_LARGE 5
+#define SST_LEN_SOLVED 6
+typedef struct sst_length_program_args {
+  int64_t n_spec;
+  int64_t n_cand;               /* cand_off[n_spec] */
+  const int32_t* max_len;       /* [n_spec] M */
+  const int64_t* skel_off;      /* [n_spec + 1] in positions: spectrum g holds 2 M */
+  const uint64_t* skeleton;     /* [2 skel_off[n_spec]] two u64 per position */
+  const uint64_t* alpha;        /* [2 n_spec] */
+  const int64_t* frag_off;      /* [n_spec + 1] */
+  const uint8_t* frag_code;     /* [frag_off[n_spec]] each */
+  const double* frag_su;
+  const int32_t* frag_min_end;  /* the walk's raw ends */
+  const int32_t* frag_max_end;
+  const int64_t* cand_off;      /* [n_spec + 1] */
+  const int32_t* cand_len;      /* [n_cand] each */
+  const uint8_t* valid;
+  const int32_t* mod_cap;
+  double prec;
+  const uint8_t* row_mod;       /* [table rows] */
+  const int32_t* row_cap;       /* [254 * table rows] */
+  uint64_t max_combos;
+  uint8_t* status;              /* outputs, [n_cand] each */
+  uint64_t* combos;
+  uint64_t* n_feas;
+  uint64_t* best;
+} sst_length_program_args;
+int sst_length_program_device(sst_table* t, const sst_length_program_args* a);
+
 /* compute_sequence_length_bound (mass_table.py:343-487) after the skeleton's
  * alphabet reduction (skeleton_building.py:315-336), both directions, for
  * queries on per-spectrum reduced alphabets, exact without a table rebuild:
@@ -1582,7 +1703,8 @@ int64_t sst_pyset_order(const int32_t* keys, const int64_t* hashes, int64_t n, i
 #define SST_K_FINAL 27 /* k_final_program (sst_final_program_device) */
 #define SST_K_FINAL_ROBUST 28 /* k_final_robust (sst_final_robust_device) */
 #define SST_K_FINAL_SEARCH 29 /* k_final_search_list / k_final_search (sst_final_search_device) */
-#define SST_K_COUNT 30
+#define SST_K_LENGTH_PROGRAM 30 /* k_length_program (sst_length_program_device) */
+#define SST_K_COUNT 31
 /* When enabled, every kernel launch of this ctx is bracketed by hipEvents
  * recorded on the ctx stream; sst_profile_read synchronises and returns the
  * summed milliseconds and launch counts per kernel id since the last read

@@ -43,7 +43,7 @@ EXPORTS = (
     "sst_align_windows_caps_device", "sst_align_split_caps_device",
     "sst_align_windows_keep_device", "sst_align_split_keep_device",
     "sst_final_max_combos", "sst_final_program_device", "sst_final_robust_device",
-    "sst_final_search_max_width", "sst_final_search_device",
+    "sst_final_search_max_width", "sst_final_search_device", "sst_length_program_device",
 )
 
 # kernel ids of sst_profile_read
@@ -61,7 +61,8 @@ K_ALIGN_SPLIT_KEEP = 26
 K_FINAL = 27
 K_FINAL_ROBUST = 28
 K_FINAL_SEARCH = 29
-K_COUNT = 30  # SST_K_COUNT
+K_LENGTH_PROGRAM = 30
+K_COUNT = 31  # SST_K_COUNT
 KERNEL_NAMES = {K_IS_VALID: "k_is_valid", K_EXPLAIN_SCAN: "k_explain_scan", K_EXPLAIN_DEEP: "k_explain_deferred",
                 K_EXPLAIN_EXPAND: "k_explain_expand",
                 K_RESULT_PACK: "k_result_pack",  # ids 3, 4: reserved (merged into the deferred launch)
@@ -73,7 +74,8 @@ KERNEL_NAMES = {K_IS_VALID: "k_is_valid", K_EXPLAIN_SCAN: "k_explain_scan", K_EX
                 K_ALIGN_SPLIT: "k_align_split", K_ALIGN_CAPS: "k_align_windows_caps",
                 K_ALIGN_SPLIT_CAPS: "k_align_split_caps", K_ALIGN_KEEP: "k_align_windows_keep",
                 K_ALIGN_SPLIT_KEEP: "k_align_split_keep", K_FINAL: "k_final_program",
-                K_FINAL_ROBUST: "k_final_robust", K_FINAL_SEARCH: "k_final_search"}
+                K_FINAL_ROBUST: "k_final_robust", K_FINAL_SEARCH: "k_final_search",
+                K_LENGTH_PROGRAM: "k_length_program"}
 
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
@@ -218,6 +220,22 @@ class FinalSearchArgs(ctypes.Structure):
 
 # sst_final_program_device's status per spectrum (SST_FINAL_*)
 FINAL_NONE, FINAL_SOLVED, FINAL_TOO_LARGE, FINAL_INFEASIBLE, FINAL_SKIPPED, FINAL_NOT_FREE = range(6)
+
+
+class LengthProgramArgs(ctypes.Structure):
+    """sst_length_program_args (include/sst.h): the length program over the walks' dense arrays and the candidate
+    list (device pointers)."""
+    _fields_ = [("n_spec", ctypes.c_int64), ("n_cand", ctypes.c_int64)] + \
+        [(n, ctypes.c_void_p) for n in ("max_len", "skel_off", "skeleton", "alpha", "frag_off", "frag_code", "frag_su",
+                                        "frag_min_end", "frag_max_end", "cand_off", "cand_len", "valid", "mod_cap")] + \
+        [("prec", ctypes.c_double)] + \
+        [(n, ctypes.c_void_p) for n in ("row_mod", "row_cap")] + \
+        [("max_combos", ctypes.c_uint64)] + \
+        [(n, ctypes.c_void_p) for n in ("status", "combos", "n_feas", "best")]
+
+
+# sst_length_program_device's status per candidate (SST_LEN_*)
+LEN_INVALID, LEN_RAISES, LEN_NOT_MODELLED, LEN_INFEASIBLE, LEN_NOT_FREE, LEN_TOO_LARGE, LEN_SOLVED = range(7)
 
 
 class RequeryMergeArgs(ctypes.Structure):
@@ -443,6 +461,8 @@ def load_library(path=LIB_PATH):
     lib.sst_final_search_max_width.restype = ctypes.c_uint32
     lib.sst_final_search_device.argtypes = [_P, ctypes.POINTER(FinalSearchArgs)]
     lib.sst_final_search_device.restype = _I
+    lib.sst_length_program_device.argtypes = [_P, ctypes.POINTER(LengthProgramArgs)]
+    lib.sst_length_program_device.restype = _I
     lib.sst_jaccard_device.argtypes = [_P, ctypes.POINTER(JaccardArgs)]
     lib.sst_jaccard_device.restype = _I
     lib.sst_skeleton_alpha_device.argtypes = [_P, _I64, _P, _P, _P, _P, _P]

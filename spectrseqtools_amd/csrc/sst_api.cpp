@@ -3782,6 +3782,34 @@ extern "C" int sst_final_search_device(sst_table* t, const sst_final_search_args
   return SST_OK;
 }
 
+extern "C" int sst_length_program_device(sst_table* t, const sst_length_program_args* a) {
+  if (!t) return SST_E_ARG;
+  const std::string who = __func__;
+  if (!a) return fail(t->ctx, SST_E_ARG, who + ": a NULL sst_length_program_args");
+  if (a->n_spec < 0 || a->n_spec > INT32_MAX) return fail(t->ctx, SST_E_ARG, who + ": n_spec");
+  if (a->n_cand < 0 || a->n_cand > INT32_MAX) return fail(t->ctx, SST_E_ARG, who + ": n_cand");
+  if (!std::isfinite(a->prec) || !(a->prec > 0))
+    return fail(t->ctx, SST_E_ARG, who + ": prec is not a positive finite number");
+  if (a->max_combos < 1 || a->max_combos > SST_FINAL_MAX_COMBOS)
+    return fail(t->ctx, SST_E_ARG, who + ": max_combos outside [1, sst_final_max_combos()]");
+  if (a->n_spec == 0) return SST_OK;
+  if (!a->max_len || !a->skel_off || !a->skeleton || !a->alpha || !a->frag_off || !a->frag_code || !a->frag_su ||
+      !a->frag_min_end || !a->frag_max_end || !a->cand_off || !a->cand_len || !a->valid || !a->mod_cap || !a->row_mod ||
+      !a->row_cap || !a->status || !a->combos || !a->n_feas || !a->best)
+    return fail(t->ctx, SST_E_ARG, who + ": a NULL member of sst_length_program_args");
+  if (t->n_rows > SST_MAX_ROWS) return fail(t->ctx, SST_E_ARG, who + ": more than SST_MAX_ROWS rows");
+  for (int r = 0; r < t->n_rows; ++r)  // sums of 253 positions stay below 2^32
+    if (t->masses[r] < 0 || t->masses[r] >= (int64_t)(0x100000000ull / 253))
+      return fail(t->ctx, SST_E_ARG, who + ": a row mass outside [0, 2^32 / 253)");
+  if (a->n_cand == 0) return SST_OK;
+  sst_ctx* c = t->ctx;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  if (int e = set_device(c)) return e;
+  Prof p(c, SST_K_LENGTH_PROGRAM);
+  HIP_OK(c, sst::launch_length_program(*a, t->args.w, t->n_rows, 3 * c->n_cu, c->stream));
+  return SST_OK;
+}
+
 extern "C" int sst_skeleton_alpha_device(sst_table* t, int64_t n_spec, const int32_t* d_max_len,
                                          const uint64_t* d_skel_off, const uint64_t* d_skel, const uint64_t* d_alpha,
                                          uint64_t* d_out) {

@@ -719,6 +719,9 @@ hipError_t launch_final_robust(const sst_final_robust_args& r, const int* w, int
 uint64_t final_search_ws_words(uint32_t max_width);
 hipError_t launch_final_search(const sst_final_search_args& x, const int* w, int n_rows, uint32_t* list, uint32_t* ws,
                                int n_wg, hipStream_t st);
+// the length program by exact enumeration (k_length_program, sst_length_program.hip): one (spectrum, candidate) pair
+// per workgroup, n_wg workgroups
+hipError_t launch_length_program(const sst_length_program_args& a, const int* w, int n_rows, int n_wg, hipStream_t st);
 hipError_t launch_skel_alpha(int64_t n_spec, const int32_t* max_len, const uint64_t* skel_off, const uint64_t* skel,
                              const uint64_t* alpha, uint64_t canon0, uint64_t canon1, uint64_t* out, hipStream_t st);
 hipError_t launch_result_refs(const int8_t* status, int64_t n, const uint4* hits, uint64_t n_hits,

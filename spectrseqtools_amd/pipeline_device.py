@@ -1731,7 +1731,7 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
               intensity_cutoff=0.5e6, mass_cutoff=50000, limits=DeviceLimits(), fallback="mirror", name_hash=None,
               trim=True, explanation_masses=None, record=None, align=False, align_split=False, align_caps=False,
               align_keep=False, align_final=False, final_max_combos=None, align_robust=False, align_search=False,
-              search_horizon=None, search_width=None):
+              search_horizon=None, search_width=None, length_program=False, length_max_combos=None):
     """These spectra -> what Predictor.predict holds when it reaches its MILP
     stages (prediction.py:63-103), as a BatchOutcome: the six device stages
     (classify_device, fixpoint_device, bins_device, skeleton_device,
@@ -1801,7 +1801,18 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
     (final_program.final_search_host; search_horizon, search_width: its horizon
     and max_width, None: the defaults); returns (BatchOutcome, AlignOutcome,
     FinalOutcome, RobustOutcome, SearchOutcome).  Spectra the device ran take
-    final_search_device, mirror-routed ones final_search_host."""
+    final_search_device, mirror-routed ones final_search_host.
+    length_program=True: also the length program (length_program.py: the optimum
+    of the program select_sequence_length_with_lp builds per candidate length, by
+    exact enumeration); a LengthOutcome is returned after the other results
+    (alone with the BatchOutcome: a pair).  Spectra the device ran take
+    length_program_device on length_cases of the stages' arrays (record
+    receives them as length_cases); length_max_combos (None:
+    final_program.FINAL_DEFAULT_COMBOS) bounds the assignments enumerated per
+    candidate.  The mirror does not expose its two skeletons and bounds, so a
+    mirror-routed spectrum has no candidates and is marked undecided:
+    length_decisions answers LENGTH_SOLVE for it.  No other result changes, and
+    seq_len stays the Jaccard length."""
     from .masses import EXPLANATION_MASSES, TOLERANCE
     from .pipeline import max_len_of
 
@@ -1834,6 +1845,21 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
     refuse()
     d_idx = np.flatnonzero(reason == 0)  # the spectra the device runs
     dev_out = _empty_outcome(dp_table, names, len(d_idx))
+    dev_lo = None
+    if length_program:
+        from . import length_program as length_mod
+
+        dev_lo = length_mod.LengthOutcome.not_computed(len(d_idx))
+
+    def with_length(res, n_mirrored=0, where=None):
+        """The results, and the LengthOutcome after them where it was asked for."""
+        if dev_lo is None:
+            return res
+        lo = dev_lo
+        if n_mirrored:
+            lo = length_mod.LengthOutcome.concat([dev_lo, length_mod.LengthOutcome.not_computed(n_mirrored)]).take(where)
+        return (res if isinstance(res, tuple) else (res,)) + (lo,)
+
     if len(d_idx):
         cut = np.concatenate([[0], np.cumsum(peaks[d_idx])]).astype(np.int64)
         if len(d_idx) == S:
@@ -1862,6 +1888,14 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
         reason[d_idx] |= r_dev
         refuse()
         post = post_skeleton_device(dp_table, rows, sk, ln)
+        if length_program:
+            l_cases = length_mod.length_cases(dp_table, rows, sk, ln, su_seq[d_idx])
+            dev_lo = length_mod.length_program_device(
+                dp_table, l_cases,
+                max_combos=length_mod.FINAL_DEFAULT_COMBOS if length_max_combos is None else length_max_combos)
+            dev_lo.undecided[r_dev != 0] = 1  # (the mirror's result takes their place below)
+            if record is not None:
+                record.update(length_cases=l_cases)
         act = (np.asarray(post.active[:len(d_idx)]) != 0) & (r_dev == 0)
         h = handoff_device(dp_table, rows, ln, post, active=act)
         if record is not None:
@@ -1903,10 +1937,10 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
             dev_fo = final_program.final_device(dp_table, dev_out, use=use, max_combos=combos, undecided=undecided)
     if not len(m_idx):
         if align_search:
-            return dev_out, dev_al, dev_fo, dev_ro, dev_so
+            return with_length((dev_out, dev_al, dev_fo, dev_ro, dev_so))
         if align_robust:
-            return dev_out, dev_al, dev_fo, dev_ro
-        return (dev_out, dev_al, dev_fo) if align_final else (dev_out, dev_al) if align else dev_out
+            return with_length((dev_out, dev_al, dev_fo, dev_ro))
+        return with_length((dev_out, dev_al, dev_fo) if align_final else (dev_out, dev_al) if align else dev_out)
     mirrored = [mirror_outcome(dp_table, obs[offsets[g]:offsets[g + 1]], su_seq[g], seq_mass[g], max_len[g],
                                breakage_dict, None if inten is None else inten[offsets[g]:offsets[g + 1]],
                                intensity_cutoff, mass_cutoff, em, int(reason[g])) for g in m_idx.tolist()]
@@ -1938,11 +1972,12 @@ def run_batch(dp_table, obs, offsets, su_seq, seq_mass, breakage_dict, max_len=N
                 m_fo.append(f)
             fo = final_program.FinalOutcome.concat([dev_fo] + m_fo).take(where)
             if align_search:
-                return (both.take(where), al.take(where), fo,
-                        final_program.RobustOutcome.concat([dev_ro] + m_ro).take(where),
-                        final_program.SearchOutcome.concat([dev_so] + m_so).take(where))
+                return with_length((both.take(where), al.take(where), fo,
+                                    final_program.RobustOutcome.concat([dev_ro] + m_ro).take(where),
+                                    final_program.SearchOutcome.concat([dev_so] + m_so).take(where)), len(m_idx), where)
             if align_robust:
-                return both.take(where), al.take(where), fo, final_program.RobustOutcome.concat([dev_ro] + m_ro).take(where)
-            return both.take(where), al.take(where), fo
-        return both.take(where), al.take(where)
-    return both.take(where)
+                return with_length((both.take(where), al.take(where), fo,
+                                    final_program.RobustOutcome.concat([dev_ro] + m_ro).take(where)), len(m_idx), where)
+            return with_length((both.take(where), al.take(where), fo), len(m_idx), where)
+        return with_length((both.take(where), al.take(where)), len(m_idx), where)
+    return with_length(both.take(where), len(m_idx), where)

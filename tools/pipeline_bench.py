@@ -50,7 +50,7 @@ GPU-busy share of its wall time.
 
 Usage: python tools/pipeline_bench.py [--spectra 100000] [--seed 7] [--host-driven]
        [--backend nccl|gloo] [--dump-outcomes DIR] [--as-rank R] [--handoff [--handoff-repeats 3]]
-       [--align | --align-split] [--align-caps | --align-keep] [--align-final] [--align-robust | --align-search] [--modification-rate 0.5]
+       [--align | --align-split] [--align-caps | --align-keep] [--align-final] [--align-robust | --align-search] [--length-program] [--modification-rate 0.5]
 """
 import argparse
 import json
@@ -388,6 +388,56 @@ def final_stage(dp, out, al, kernels, max_combos):
             "kernel_ms": {"k_final_program": kern.get("k_final_program", (0.0, 0))[0]}}
 
 
+def length_program_stage(pd, dp, rows, sk, ln, su_seq, kernels, max_combos):
+    """--length-program: the length program (length_program.length_cases +
+    length_program_device) over every candidate length of every spectrum: the
+    optimum of the program select_sequence_length_with_lp builds, by exact
+    enumeration.  Its seconds run from the device stages' arrays to the host
+    arrays out (downloads and the gather, the validation's f64 sums on the host,
+    uploads, k_length_program, downloads), with the gather's and the
+    validation's share beside them.  It records per decision (length_decisions)
+    the spectra and how many of them have terminal fragments, the share of
+    candidates per status, log2(combos) of the SOLVED and TOO_LARGE candidates,
+    and among the LENGTH_TAKE spectra how many take a length other than the
+    Jaccard seq_len: the number this stage exists for."""
+    from spectrseqtools_amd import length_program as lp
+
+    kernels()
+    times = {}
+    t0 = time.perf_counter()
+    cases = lp.length_cases(dp, rows, sk, ln, su_seq)
+    t1 = time.perf_counter()
+    lo = lp.length_program_device(dp, cases, max_combos=max_combos, times=times)
+    s = time.perf_counter() - t0
+    kern = kernels()
+    decision, length = lp.length_decisions(lo)
+    S = max(1, len(lo))
+    has = lo.n_frag > 0
+    jac = np.asarray(ln.seq_len)[:len(lo)]
+    jac_ok = np.asarray(ln.status)[:len(lo)] == 0
+    take = decision == lp.LENGTH_TAKE
+    n_cand = np.diff(lo.cand_off)
+    pct = lambda x: {str(p): float(np.percentile(x, p)) for p in (50, 90, 99, 100)} if len(x) else {}  # noqa: E731
+    log2 = lambda st: pct(np.log2(np.maximum(lo.combos[lo.status == st].astype(np.float64), 1.0)))  # noqa: E731
+    solved = lo.status == lp.LEN_SOLVED
+    return {"s": s, "gather_s": t1 - t0, "valid_s": times.get("valid_s", 0.0), "spectra": int(len(lo)),
+            "candidates": int(len(lo.status)), "max_combos": int(max_combos),
+            "candidates_per_spectrum": pct(n_cand), "spectra_with_fragments": int(has.sum()),
+            "decisions": {name: {"spectra": int((decision == d).sum()), "share": float((decision == d).sum()) / S,
+                                 "with_fragments_share": float(has[decision == d].mean()) if (decision == d).any() else 0.0}
+                          for d, name in lp.DECISION_NAMES.items()},
+            "status_shares": lo.shares(),
+            "status_counts": {name: int((lo.status == st).sum()) for st, name in lp.STATUS_NAMES.items()},
+            "take_spectra": int(take.sum()),
+            "take_differs_from_jaccard": int((take & (length != jac)).sum()),
+            "take_where_jaccard_found_no_length": int((take & ~jac_ok).sum()),
+            "jaccard_decisions_where_jaccard_found_a_length": int(((decision == lp.LENGTH_JACCARD) & jac_ok).sum()),
+            "log2_combos_solved": log2(lp.LEN_SOLVED), "log2_combos_too_large": log2(lp.LEN_TOO_LARGE),
+            "assignments_enumerated": int(lo.combos[solved].sum()), "spectra_are": "synthetic (spectrseqtools_amd.synthetic)",
+            "path": "device (sst_length_program_device), the stages' device arrays in, host arrays out",
+            "kernels": kern, "kernel_ms": {"k_length_program": kern.get("k_length_program", (0.0, 0))[0]}}
+
+
 def free_positions(out):
     """Free positions (|A_i| > 1) per spectrum of a BatchOutcome (i64)."""
     spec = np.repeat(np.arange(len(out)), np.diff(out.pos_off))
@@ -700,6 +750,12 @@ def main():
     ap.add_argument("--final-max-combos", type=int, default=1 << 20,
                     help="--align-final, --align-robust: assignments enumerated per spectrum at most (up to 2^22; "
                          "--align-search: 0 searches every spectrum)")
+    ap.add_argument("--length-program", action="store_true",
+                    help="after post_skeleton: the length program (select_sequence_length_with_lp by exact enumeration) "
+                         "over every candidate length of every spectrum, its decisions and how many TAKE lengths "
+                         "differ from the Jaccard length")
+    ap.add_argument("--length-max-combos", type=int, default=1 << 20,
+                    help="--length-program: assignments enumerated per candidate at most (up to 2^22)")
     ap.add_argument("--modification-rate", type=float, default=0.5,
                     help="the sequences' universal modification rate: the synthetic spectra's and the table's "
                          "SequenceInformation's (0.05: the low-modification-rate variant)")
@@ -803,6 +859,8 @@ def main():
         # batches; the timed stage reuses the warm-up's, as round 5 did)
         lw = pd.length_device(dp, kw, bw.alpha_dev, su_seq[:S0], batch.seq_mass[:S0], trim=False)
         pw = pd.post_skeleton_device(dp, rw, kw, lw)
+        if args.length_program:
+            length_program_stage(pd, dp, rw, kw, lw, su_seq[:S0], lambda: {}, args.length_max_combos)
         if args.align:
             held = {}
             align_stage(pd, dp, rw, lw, pw, lambda: {}, split=args.align_split, caps=args.align_caps, keep=args.align_keep,
@@ -977,6 +1035,12 @@ def main():
         stages["gather"] = {"s": tmax(time.perf_counter() - t0), "bytes_per_rank": sizes, "kernels": kernels(),
                             "path": "pack_outcomes + one agreed-size gather to rank 0"
                                     + (f" ({'RCCL' if args.backend == 'nccl' else 'gloo'})" if dist else " (local)")}
+    if rows is not None and args.length_program:
+        barrier()
+        stages["length_program"] = length_program_stage(pd, dp, rows, sk, ln, su_seq, kernels, args.length_max_combos)
+        stages["length_program"]["s"] = tmax(stages["length_program"]["s"])
+        busy(stages["length_program"])
+        progress("length_program")
     if rows is not None and args.align:
         barrier()
         held = {}
