@@ -152,8 +152,14 @@ def when(cond):
     return _When(cond)
 
 
-def concat(frames):
+def concat(frames, how="vertical"):
+    if how == "horizontal":  # (LinearProgramInstance.evaluate's fragment table)
+        return DataFrame(pd.concat([f._d for f in frames], axis=1))
     return DataFrame(pd.concat([f._d for f in frames], ignore_index=True))
+
+
+def from_dicts(rows):
+    return DataFrame(pd.DataFrame(list(rows)))
 
 
 class Series(list):
@@ -240,7 +246,12 @@ class DataFrame:
         return Series(self._d[name].tolist())
 
     def __getitem__(self, name):
+        if isinstance(name, (int, np.integer)):  # one row as a frame (filter_with_lp's fragments[idx])
+            return DataFrame(self._d.iloc[[int(name)]])
         return Series(self._d[name].tolist())
+
+    def select(self, *exprs):
+        return DataFrame(pd.DataFrame({e.name: np.asarray(e.fn(self)) for e in exprs}))
 
     def rows(self):
         return [tuple(r) for r in self._d.itertuples(index=False)]
